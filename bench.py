@@ -22,8 +22,21 @@ reduce, done with torch.distributed all_reduce (RCCL over xGMI), mirroring
 the client-side fan-out+aggregate of the reference
 (src/client_lib/pegasus_client_impl.cpp:1197-1267).
 
-CPU baseline: the CPU oracle (restatement of the reference path)
-timed on a bounded sample on this box's host cores — reported, not the target.
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the
+headline figure needs: setup, W warmup steps, N timed steps, the optional
+--dump-outputs write, and the one JSON result line.  Everything else — the
+instrumented per-call step and in-engine roofline, the count-scan / point-get
+/ YCSB C+E side measurements, the C++-host serving bench and the CPU-oracle
+baseline (restatement of the reference path; SURVEY §8(d), timed on a bounded
+sample on the host's cores — reported, not the target) — runs only with --full
+and lands in the result line's `roofline`, `cpu_baseline` and `extra` fields.
+
+--dump-outputs DIR writes what the last timed step returned to its caller:
+DIR/compact_stats.npy, float64 [partitions, 8] = per partition the status
+code and the seven rrdb_compact_stats counters (the merged run itself stays
+in HBM and is freed by the engine; keep_inputs passes hand back only these).
+Inputs are seeded, so two builds run with the same arguments are comparable
+output for output.
 """
 import argparse
 import json
@@ -113,7 +126,16 @@ def main():
     ap.add_argument("--rules-profile", action="store_true",
                     help="configs[4] shape: TTL'd data + default_ttl + user "
                          "delete/update-TTL compaction rules evaluated per key")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements (roofline, scan/get/YCSB legs, "
+                         "C++-host serving bench, CPU-oracle baseline); a plain run "
+                         "times only the headline compaction steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's outputs "
+                         "to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -179,28 +201,27 @@ def main():
     # pool over per-partition streams was measured 4x SLOWER (multi-threaded
     # HIP submission + sync contention: 256 vs 64 ms/step); this keeps one
     # submitting thread.
+    # returns what the caller of the compaction path receives: every
+    # partition's (status, stats), in partition order
     def one_step():
-        out_records = 0
-        st = None
+        results = []
         for eng in parts:
             assert eng.manual_compact_begin(epoch_now, keep_inputs=True) == 0
         for eng in parts:
             err, st = eng.manual_compact_finish()
             assert err == 0
-            out_records += st.output_records
-        return out_records, st
+            results.append((err, st))
+        return results
 
     # ---- warmup ----
     for _ in range(args.warmup):
-        out_records, last_stats = one_step()
-    if args.warmup == 0:
-        out_records, last_stats = one_step()  # need sizes for roofline math
+        one_step()
 
     # ---- timed region: K compaction passes ----
     barrier_sync()
     t0 = time.time()
     for _ in range(args.steps):
-        one_step()
+        step_results = one_step()
     barrier_sync()
     elapsed = time.time() - t0
     if dist:
@@ -212,6 +233,53 @@ def main():
     keys_per_step_job = total_records * max(world, 1)  # whole-job aggregate
     value = keys_per_step_job * args.steps / elapsed
     ms_per_step = elapsed * 1000.0 / args.steps
+    # sizes for the result line / roofline math come from the last timed step
+    out_records = sum(st.output_records for _, st in step_results)
+    last_stats = step_results[-1][1]
+
+    if args.dump_outputs:
+        from incubator_pegasus_amd.capi import _CompactStats
+
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        table = np.array([[err] + [getattr(st, f[0]) for f in _CompactStats._fields_]
+                          for err, st in step_results], dtype=np.float64)
+        name = "compact_stats" if world <= 1 else f"compact_stats_rank{rank}"
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), table)
+
+    result = {
+        "metric": "compaction keys/sec per node",
+        "value": round(value, 1),
+        "unit": "keys/s",
+        "n_gpus": max(world, 1),
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 2),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,  # no published reference number
+        "dtype": "u8",
+        "data": "synthetic",
+        "config": {
+            "workload": ("compact-50M-16part-8run" if args.keys == 50_000_000 else
+                         f"compact-{args.keys}-{args.partitions}part-{args.runs}run")
+                        + ("-ttl-rules" if args.rules_profile else ""),
+            "partitions_per_gpu": args.partitions,
+            "keys_per_gpu": total_records,
+            "runs_per_partition": args.runs,
+            "record_bytes": 130,
+            "hashkey_bytes": 16,
+            "value_bytes": 100,
+            "value_schema": "v1",
+        },
+    }
+    if not args.full:
+        for eng in parts:
+            eng.close()
+        if rank == 0:
+            print(json.dumps(result))
+        return
+
+    # ==== everything below runs only with --full ====
 
     # one instrumented (untimed) step: per-call wall vs in-kernel time
     call_ms = []
@@ -511,31 +579,7 @@ def main():
         eng.close()
 
     if rank == 0:
-        line = {
-            "metric": "compaction keys/sec per node",
-            "value": round(value, 1),
-            "unit": "keys/s",
-            "n_gpus": max(world, 1),
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 2),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,  # no published reference number
-            "dtype": "u8",
-            "data": "synthetic",
-            "config": {
-                "workload": ("compact-50M-16part-8run" if args.keys == 50_000_000 else
-                             f"compact-{args.keys}-{args.partitions}part-{args.runs}run")
-                            + ("-ttl-rules" if args.rules_profile else ""),
-                "partitions_per_gpu": args.partitions,
-                "keys_per_gpu": total_records,
-                "runs_per_partition": args.runs,
-                "record_bytes": 130,
-                "hashkey_bytes": 16,
-                "value_bytes": 100,
-                "value_schema": "v1",
-            },
+        result.update({
             "roofline": roofline,
             "cpu_baseline": cpu_baseline,
             "extra": {
@@ -551,8 +595,8 @@ def main():
                 "ycsb_e_prefix_multi_get": ycsb_e,
                 "cpu_single_core": cpu_aux,
             },
-        }
-        print(json.dumps(line))
+        })
+        print(json.dumps(result))
 
 
 if __name__ == "__main__":

@@ -6,17 +6,30 @@ standalone (oracle/_ref/libcrc_ref.so — built by oracle/Makefile from
 Run in the container that has the reference tree; the committed JSON travels
 to GPU boxes where the reference is absent.
     python tests/golden/gen_crc64_golden.py > tests/golden/crc64_golden.json
+    python tests/golden/gen_crc64_golden.py ref-build > tests/golden/crc64_ref_build.json
+(the second form records the answers for the seeded case sequence of
+tests/test_crc64.py::test_crc64_vs_reference_build)
 """
 import ctypes
 import json
 import os
 import random
+import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 ref = ctypes.CDLL(os.path.join(REPO, "oracle", "_ref", "libcrc_ref.so"))
 f = getattr(ref, "_ZN3dsn5utils10crc64_calcEPKvmm")  # dsn::utils::crc64_calc
 f.restype = ctypes.c_uint64
 f.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint64]
+
+if sys.argv[1:] == ["ref-build"]:
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    from test_crc64 import _ref_build_cases
+
+    print(json.dumps({"source": "reference src/utils/crc.cpp compiled standalone (oracle/_ref)",
+                      "cases": "tests/test_crc64.py::_ref_build_cases (seeded)",
+                      "crc": [f(b, len(b), init) for b, init in _ref_build_cases()]}, indent=0))
+    sys.exit(0)
 
 rnd = random.Random(20260915)
 cases = []

@@ -4,8 +4,6 @@ import ctypes
 import os
 import random
 
-import pytest
-
 from conftest import ORACLE_SO, REF_CRC_SO
 from pymodel import crc64 as py_crc64
 
@@ -17,20 +15,39 @@ def _orc():
     return lib
 
 
-def test_crc64_vs_reference_build():
-    if not os.path.exists(REF_CRC_SO):
-        pytest.skip("oracle/_ref not built (reference tree absent and no prebuilt _ref)")
-    orc = _orc()
-    ref = ctypes.CDLL(REF_CRC_SO)
-    f = getattr(ref, "_ZN3dsn5utils10crc64_calcEPKvmm")  # dsn::utils::crc64_calc
-    f.restype = ctypes.c_uint64
-    f.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint64]
+def _ref_build_cases():
+    """The 500 seeded (data, init) cases of test_crc64_vs_reference_build;
+    tests/golden/gen_crc64_golden.py records the reference build's answers
+    for exactly this sequence."""
     rnd = random.Random(20260915)
     for _ in range(500):
         n = rnd.randrange(0, 100)
         b = bytes(rnd.randrange(256) for _ in range(n))
         init = rnd.choice([0, 0xFFFFFFFFFFFFFFFF, rnd.getrandbits(64)])
-        assert orc.orc_crc64(b, n, init) == f(b, n, init)
+        yield b, init
+
+
+def test_crc64_vs_reference_build():
+    """Every case is checked against the answers recorded from the reference
+    build (tests/golden/crc64_ref_build.json) and, where oracle/_ref is
+    built, against that library itself as well."""
+    import json
+
+    path = os.path.join(os.path.dirname(__file__), "golden", "crc64_ref_build.json")
+    recorded = json.load(open(path))["crc"]
+    assert len(recorded) == 500
+    orc = _orc()
+    f = None
+    if os.path.exists(REF_CRC_SO):
+        ref = ctypes.CDLL(REF_CRC_SO)
+        f = getattr(ref, "_ZN3dsn5utils10crc64_calcEPKvmm")  # dsn::utils::crc64_calc
+        f.restype = ctypes.c_uint64
+        f.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint64]
+    for (b, init), want in zip(_ref_build_cases(), recorded):
+        got = orc.orc_crc64(b, len(b), init)
+        assert got == want
+        if f is not None:
+            assert got == f(b, len(b), init)
 
 
 def test_crc64_vs_pymodel():
