@@ -146,9 +146,11 @@ typedef struct {
 
 /* manual compaction options — the subset of rocksdb::CompactRangeOptions that
  * do_manual_compact builds (reference pegasus_server_impl.cpp:3373-3420,
- * pegasus_manual_compact_service.cpp:231-271).  Our engine always merges all
+ * pegasus_manual_compact_service.cpp:231-271).  The manual pass merges all
  * runs of the partition into one (CompactRange over the full range with
- * bottommost_level_compaction=force ≡ tombstones dropped). */
+ * bottommost_level_compaction=force ≡ tombstones dropped).  Merging only a
+ * sub-range of the runs, tombstones retained, is an engine-only extension
+ * declared in rrdb_engine_ext.h. */
 typedef struct {
     int32_t target_level;          /* -1 = bottommost (informational) */
     uint8_t bottommost_force;      /* 1 = force (default in reference) */

@@ -226,6 +226,18 @@ class RrdbLib:
         L.rrdb_num_records.restype = C.c_uint64
         L.rrdb_num_records.argtypes = [C.c_void_p]
         L.rrdb_free_result.argtypes = [C.POINTER(_Result)]
+        # engine-only extensions (include/rrdb_engine_ext.h): bound only when
+        # the loaded library exports them (the CPU oracle does not)
+        self.has_window_compact = all(
+            hasattr(L, n) for n in ("rrdb_compact_runs", "rrdb_auto_compact"))
+        if self.has_window_compact:
+            L.rrdb_compact_runs.restype = C.c_int32
+            L.rrdb_compact_runs.argtypes = [
+                C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(_CompactStats)]
+            L.rrdb_auto_compact.restype = C.c_int32
+            L.rrdb_auto_compact.argtypes = [
+                C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                C.POINTER(_CompactStats)]
 
     @property
     def backend(self) -> str:
@@ -583,3 +595,31 @@ class RrdbPartition:
         err = self._L.rrdb_manual_compact_finish(self._h, C.byref(st))
         stats = CompactStats(**{f[0]: getattr(st, f[0]) for f in _CompactStats._fields_})
         return err, stats
+
+    # ---- window (minor) compaction: engine-only (include/rrdb_engine_ext.h) ----
+    def _need_window_compact(self, what: str):
+        if not self.lib.has_window_compact:
+            raise RuntimeError(
+                f"{what}: backend {self.lib.backend!r} ({self.lib.path}) does not export "
+                "rrdb_compact_runs/rrdb_auto_compact (engine-only extensions)")
+
+    def compact_runs(self, first: int, n: int, epoch_now: int):
+        """Merge runs [first, first+n) (0 = oldest) into one run in their
+        place; bottommost iff first == 0.  Returns (err, CompactStats), like
+        manual_compact."""
+        self._need_window_compact("compact_runs")
+        st = _CompactStats()
+        err = self._L.rrdb_compact_runs(self._h, first, n, epoch_now, C.byref(st))
+        stats = CompactStats(**{f[0]: getattr(st, f[0]) for f in _CompactStats._fields_})
+        return err, stats
+
+    def auto_compact(self, epoch_now: int):
+        """Background-compaction tick.  Returns (err, first, n, CompactStats);
+        n == 0 means nothing was compacted."""
+        self._need_window_compact("auto_compact")
+        st = _CompactStats()
+        first, n = C.c_uint64(0), C.c_uint64(0)
+        err = self._L.rrdb_auto_compact(self._h, epoch_now, C.byref(first), C.byref(n),
+                                        C.byref(st))
+        stats = CompactStats(**{f[0]: getattr(st, f[0]) for f in _CompactStats._fields_})
+        return err, first.value, n.value, stats

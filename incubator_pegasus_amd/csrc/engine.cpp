@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "../../include/rrdb_engine.h"
+#include "../../include/rrdb_engine_ext.h"
 #include "engine_common.h"
 
 /* ---- launchers (kernels.hip) ---- */
@@ -626,6 +627,12 @@ struct HipEngine {
     hipStream_t stream = nullptr;
     uint32_t data_version = 1, default_ttl = 0;
     bool validate_hash = false, manual_compact_disabled = false;
+    /* background-compaction tick (rrdb_auto_compact): run-count trigger (env
+     * "engine.l0_compaction_trigger", the reference's
+     * level0_file_num_compaction_trigger) and the bulk_load usage scenario,
+     * which switches the tick off */
+    uint32_t l0_trigger = 4;
+    bool bulk_load = false;
     bool bloom_enabled = true; /* env "rocksdb.filter_type": common(default)|none */
     uint32_t max_iter_count = 1000, mg_max_iter_count = 3000;
     uint64_t mg_max_iter_size = 30ull << 20, iter_time_ms = 30000;
@@ -637,6 +644,9 @@ struct HipEngine {
      * device pointers are arena memory, valid until the next scratch_reset */
     struct PendingCompact {
         bool active = false, trivial = false, keep_inputs = false;
+        /* the pass merges runs [first, first+R); bottommost iff first == 0 */
+        bool bottommost = true, chunked = false;
+        size_t first = 0;
         int R = 0;
         uint64_t total = 0;
         DevRun *dr = nullptr;
@@ -894,30 +904,49 @@ struct HipEngine {
             return false;
         if (ldst_elig_cache >= 0)
             return ldst_elig_cache != 0;
-        ldst_elig_cache = 0;
-        uint32_t fk = runs[0].fixed_klen;
+        ldst_elig_cache = word_eligible_range(0, runs.size()) ? 1 : 0;
+        return ldst_elig_cache != 0;
+    }
+    /* the same test over runs [first, first+n) only (a window compaction
+     * ranks just those); never reads or writes the whole-set cache */
+    bool word_eligible_range(size_t first, size_t n)
+    {
+        if (n < 2)
+            return false;
+        uint32_t fk = runs[first].fixed_klen;
         if (fk < 8)
             return false;
-        for (auto &rr : runs)
-            if (!rr.tails || rr.fixed_klen != fk || rr.n == 0)
+        for (size_t ri = first; ri < first + n; ri++)
+            if (!runs[ri].tails || runs[ri].fixed_klen != fk || runs[ri].n == 0)
                 return false;
         if (fk > 8) {
             uint8_t p0[32], pi[32];
             uint64_t pl = fk - 8 < 32 ? fk - 8 : 32;
-            HIP_OK(hipMemcpy(p0, runs[0].keys, pl, hipMemcpyDeviceToHost));
-            for (size_t ri = 1; ri < runs.size(); ri++) {
+            HIP_OK(hipMemcpy(p0, runs[first].keys, pl, hipMemcpyDeviceToHost));
+            for (size_t ri = first + 1; ri < first + n; ri++) {
                 HIP_OK(hipMemcpy(pi, runs[ri].keys, pl, hipMemcpyDeviceToHost));
                 if (memcmp(p0, pi, pl) != 0)
                     return false;
             }
         }
-        ldst_elig_cache = 1;
         return true;
+    }
+    bool window_word_eligible(size_t first, size_t n)
+    {
+        return (first == 0 && n == runs.size()) ? word_eligible() : word_eligible_range(first, n);
     }
     bool ldst_eligible() { return rank_mode == 3 && word_eligible(); }
     bool grp_eligible()
     {
         return rank_mode == 4 && runs.size() <= LDST_MAXR && word_eligible();
+    }
+    bool ldst_eligible(size_t first, size_t n)
+    {
+        return rank_mode == 3 && window_word_eligible(first, n);
+    }
+    bool grp_eligible(size_t first, size_t n)
+    {
+        return rank_mode == 4 && n <= LDST_MAXR && window_word_eligible(first, n);
     }
 
     void free_run(RunBuf &r)
@@ -1593,6 +1622,14 @@ int32_t rrdb_set_envs(void *h, const char *const *keys, const char *const *value
             }
         } else if (k == "engine.emit_mode") {
             e->emit_mode = (v == "input") ? 1 : (v == "rank" ? 0 : 2);
+        } else if (k == "engine.l0_compaction_trigger") {
+            long long t = atoll(v.c_str());
+            e->l0_trigger = t < 2 ? 2u : (uint32_t)std::min<long long>(t, UINT32_MAX);
+        } else if (k == "rocksdb.usage_scenario") {
+            /* bulk_load sets level0_file_num_compaction_trigger to -1, i.e.
+             * no automatic compaction (set_usage_scenario); normal and
+             * prefer_write leave it on */
+            e->bulk_load = (v == "bulk_load");
         }
     }
     return RRDB_OK;
@@ -2911,7 +2948,17 @@ int32_t rrdb_multi_get(void *h, const rrdb_multi_get_request *q, uint32_t epoch_
  * runs per-replica compactions concurrently on THREAD_POOL_COMPACT —
  * pegasus_server_impl.cpp:3373): submit rank + prefix sums + async size
  * reads, NO host-blocking sync.  Caller holds the handle lock. */
-static int32_t compact_begin(HipEngine *e, const rrdb_compact_options *opts, uint32_t epoch_now)
+/* The pass merges the window [first, first+n) of e->runs (0 = oldest) into
+ * one run that takes the window's place; it is bottommost iff first == 0.
+ * win == nullptr is the manual pass: every run, honouring
+ * manual_compact.disabled and engine.emit_mode.  A window pass (the caller
+ * validated it after flushing) always takes the chunked emit, the only one
+ * that knows converted tombstones. */
+struct CompactWindow {
+    size_t first, n;
+};
+static int32_t compact_begin(HipEngine *e, const rrdb_compact_options *opts, uint32_t epoch_now,
+                             const CompactWindow *win = nullptr)
 {
     if (e->pend.active)
         return RRDB_INVALID_ARGUMENT;
@@ -2919,13 +2966,17 @@ static int32_t compact_begin(HipEngine *e, const rrdb_compact_options *opts, uin
         return RRDB_IO_ERROR;
     e->scratch_reset();
     rrdb_compact_stats st{};
-    if (e->manual_compact_disabled)
+    if (!win && e->manual_compact_disabled)
         return RRDB_INVALID_ARGUMENT;
     e->activate();
-    int R = (int)e->runs.size();
+    const size_t first = win ? win->first : 0;
+    int R = (int)(win ? win->n : e->runs.size());
+    const bool bottommost = first == 0;
+    const int emit_mode = win ? 2 : e->emit_mode;
+    const RunBuf *wr = e->runs.data() + first; /* the window's runs */
     uint64_t total = 0;
-    for (auto &r : e->runs)
-        total += r.n;
+    for (int r = 0; r < R; r++)
+        total += wr[r].n;
     st.input_records = total;
     if (total == 0) {
         e->pend = {};
@@ -2934,14 +2985,15 @@ static int32_t compact_begin(HipEngine *e, const rrdb_compact_options *opts, uin
         e->pend.st = st;
         return RRDB_OK;
     }
-    DevRun *dr = e->dev_runs();
+    /* run ids in order[] are relative to this pointer, i.e. to the window */
+    DevRun *dr = e->dev_runs() + first;
     /* full-range rank merge */
     std::vector<uint64_t> lo(R, 0), hi(R), wprefix(R + 1);
     uint64_t acc = 0;
     for (int r = 0; r < R; r++) {
-        hi[r] = e->runs[r].n;
+        hi[r] = wr[r].n;
         wprefix[r] = acc;
-        acc += e->runs[r].n;
+        acc += wr[r].n;
     }
     wprefix[R] = acc;
     uint64_t *d_lo = (uint64_t *)e->upload_tmp(lo.data(), R * 8);
@@ -2966,23 +3018,28 @@ static int32_t compact_begin(HipEngine *e, const rrdb_compact_options *opts, uin
     cp.n_ops = e->n_ops;
     cp.rules = e->d_rules;
     cp.pats = e->d_pats;
+    cp.bottommost = bottommost ? 1 : 0;
 
     /* all-fixed-stride fast mode: every run shares one key and one value
      * stride (the hashkey-table schema), so output offsets derive from the
      * keep count — the ksz/vsz arrays and two of the three full-length
      * prefix sums are skipped entirely */
-    uint64_t ffk = e->runs.empty() ? 0 : e->runs[0].fixed_klen;
-    uint64_t ffv = e->runs.empty() ? 0 : e->runs[0].fixed_vlen_put;
-    for (auto &rr : e->runs) {
-        if (rr.fixed_klen != ffk)
+    uint64_t ffk = R == 0 ? 0 : wr[0].fixed_klen;
+    uint64_t ffv = R == 0 ? 0 : wr[0].fixed_vlen_put;
+    for (int r = 0; r < R; r++) {
+        if (wr[r].fixed_klen != ffk)
             ffk = 0;
-        if (rr.fixed_vlen_put != ffv)
+        if (wr[r].fixed_vlen_put != ffv)
             ffv = 0;
     }
-    bool fixed_emit = ffk > 0 && ffv > 0 && e->emit_mode == 2;
+    /* a non-bottommost output can hold tombstones (kept or converted), whose
+     * rows are not fv long: it always takes the per-row-size path */
+    bool fixed_emit = ffk > 0 && ffv > 0 && emit_mode == 2 && bottommost;
     /* no default-TTL and no user ops => the filter can never rewrite a
-     * value: skip the changed/new_expire arrays and the patch pass */
-    bool no_rewrite = e->default_ttl == 0 && e->n_ops == 0 && e->emit_mode == 2;
+     * value: skip the changed/new_expire arrays and the patch pass.  Not so
+     * when non-bottommost: an expired PUT is rewritten into a tombstone and
+     * changed[] carries that marker. */
+    bool no_rewrite = e->default_ttl == 0 && e->n_ops == 0 && emit_mode == 2 && bottommost;
     uint8_t *d_changed = no_rewrite ? nullptr : e->talloc<uint8_t>(total);
     uint32_t *d_new_expire = no_rewrite ? nullptr : e->talloc<uint32_t>(total * 4);
     uint64_t *d_ksz = fixed_emit ? nullptr : e->talloc<uint64_t>(total * 8);
@@ -2991,12 +3048,12 @@ static int32_t compact_begin(HipEngine *e, const rrdb_compact_options *opts, uin
     uint64_t *d_kpos = e->talloc<uint64_t>(total * 8);
     uint64_t *d_koffs = fixed_emit ? nullptr : e->talloc<uint64_t>(total * 8);
     uint64_t *d_voffs = fixed_emit ? nullptr : e->talloc<uint64_t>(total * 8);
-    uint64_t *d_rank_of = e->emit_mode == 1 ? e->talloc<uint64_t>(total * 8) : nullptr;
+    uint64_t *d_rank_of = emit_mode == 1 ? e->talloc<uint64_t>(total * 8) : nullptr;
     /* 8 stat banks: the group rank flushes per-block tallies to bank
      * blockIdx&7; legacy kernels add to bank 0; finish sums all banks */
     CompactStatsDev *d_stats = e->talloc<CompactStatsDev>(8 * sizeof(CompactStatsDev));
     HIP_OK(hipMemsetAsync(d_stats, 0, 8 * sizeof(CompactStatsDev), e->stream));
-    if (e->rank_mode == 1 && R > 1 && e->emit_mode == 2) {
+    if (e->rank_mode == 1 && R > 1 && emit_mode == 2) {
         /* LDS-staged block rank: shift-8 bound table + per-run block counts */
         uint64_t *d_bt8_off = nullptr, *d_bt8 = nullptr;
         {
@@ -3023,7 +3080,7 @@ static int32_t compact_begin(HipEngine *e, const rrdb_compact_options *opts, uin
                                 d_keepw, d_changed, d_new_expire, d_ksz, d_vsz, d_stats,
                                 e->stream);
         HIP_OK(hipEventRecord(ev[1], e->stream));
-    } else if (R > 1 && e->emit_mode != 1 && e->grp_eligible()) {
+    } else if (R > 1 && emit_mode != 1 && e->grp_eligible(first, (size_t)R)) {
         /* group-streaming rank: no bound table; anchors partition the runs */
         uint64_t *d_anch = nullptr;
         uint64_t n_groups = e->build_anchors(dr, R, lo, hi, d_lo, d_hi, &d_anch);
@@ -3036,7 +3093,7 @@ static int32_t compact_begin(HipEngine *e, const rrdb_compact_options *opts, uin
     if (R > 1 && total > 100000)
         e->build_bound_table(dr, R, lo, hi, d_lo, d_hi, &d_bt_off, &d_bt);
     HIP_OK(hipEventRecord(ev[0], e->stream));
-    bool ldst_ok = R > 1 && e->ldst_eligible();
+    bool ldst_ok = R > 1 && e->ldst_eligible(first, (size_t)R);
     if (ldst_ok)
         launch_rank_compact_ldst(dr, R, d_lo, d_hi, d_wp, total, cp, d_order, d_keepw,
                                  d_changed, d_new_expire, d_ksz, d_vsz, d_rank_of, d_bt_off,
@@ -3073,6 +3130,9 @@ static int32_t compact_begin(HipEngine *e, const rrdb_compact_options *opts, uin
     e->pend.active = true;
     e->pend.keep_inputs = opts && opts->keep_inputs;
     e->pend.R = R;
+    e->pend.first = first;
+    e->pend.bottommost = bottommost;
+    e->pend.chunked = win != nullptr;
     e->pend.total = total;
     e->pend.dr = dr;
     e->pend.d_wp = d_wp;
@@ -3115,7 +3175,6 @@ static int32_t compact_finish(HipEngine *e, rrdb_compact_stats *stats)
         return RRDB_OK;
     }
     int R = e->pend.R;
-    (void)R;
     uint64_t total = e->pend.total;
     DevRun *dr = e->pend.dr;
     uint64_t *d_wp = e->pend.d_wp, *d_order = e->pend.d_order, *d_keepw = e->pend.d_keepw;
@@ -3146,9 +3205,13 @@ static int32_t compact_finish(HipEngine *e, rrdb_compact_stats *stats)
     st.output_records = n_out;
     st.expired = hs.expired;
     st.filtered = hs.filtered;
-    st.tombstones = hs.tombstones;
+    /* non-bottommost: no tombstone is dropped (each is in output_records);
+     * expired/filtered count the conversions */
+    st.tombstones = e->pend.bottommost ? hs.tombstones : 0;
     st.shadowed = hs.shadowed;
     st.output_bytes = kbytes + vbytes;
+    const size_t first = e->pend.first;
+    const RunBuf *wr = e->runs.data() + first; /* the window's runs */
 
     RunBuf nr;
     bool keep_inputs = e->pend.keep_inputs;
@@ -3156,24 +3219,34 @@ static int32_t compact_finish(HipEngine *e, rrdb_compact_stats *stats)
         nr.n = n_out;
         /* output keys are verbatim copies of input keys, so a stride shared
          * by every input run is preserved */
-        nr.fixed_klen = e->runs.empty() ? 0 : e->runs[0].fixed_klen;
-        for (auto &ir : e->runs)
-            if (ir.fixed_klen != nr.fixed_klen)
+        nr.fixed_klen = R == 0 ? 0 : wr[0].fixed_klen;
+        for (int r = 0; r < R; r++)
+            if (wr[r].fixed_klen != nr.fixed_klen)
                 nr.fixed_klen = 0;
         /* output values are verbatim-length copies of input values, so a
          * stride shared by every input run is preserved too */
-        nr.fixed_vlen = e->runs.empty() ? 0 : e->runs[0].fixed_vlen;
-        for (auto &ir : e->runs)
-            if (ir.fixed_vlen != nr.fixed_vlen)
+        nr.fixed_vlen = R == 0 ? 0 : wr[0].fixed_vlen;
+        for (int r = 0; r < R; r++)
+            if (wr[r].fixed_vlen != nr.fixed_vlen)
                 nr.fixed_vlen = 0;
-        /* the merged output holds only PUTs: its plain stride equals the
-         * shared put-stride of the inputs (when one exists) */
-        nr.fixed_vlen_put = e->runs.empty() ? 0 : e->runs[0].fixed_vlen_put;
-        for (auto &ir : e->runs)
-            if (ir.fixed_vlen_put != nr.fixed_vlen_put)
+        /* the output's PUTs are verbatim-length copies of input PUTs: the
+         * shared put-stride of the inputs (when one exists) is preserved */
+        nr.fixed_vlen_put = R == 0 ? 0 : wr[0].fixed_vlen_put;
+        for (int r = 0; r < R; r++)
+            if (wr[r].fixed_vlen_put != nr.fixed_vlen_put)
                 nr.fixed_vlen_put = 0;
-        if (!nr.fixed_vlen)
-            nr.fixed_vlen = nr.fixed_vlen_put;
+        if (e->pend.bottommost) {
+            /* the merged output holds only PUTs: its plain stride equals
+             * the put-stride */
+            if (!nr.fixed_vlen)
+                nr.fixed_vlen = nr.fixed_vlen_put;
+        } else if (hs.tombstones + hs.expired + hs.filtered > 0) {
+            /* a tombstone was emitted (kept, or converted with an empty
+             * value): the output has no plain value stride */
+            nr.fixed_vlen = 0;
+        } else if (!nr.fixed_vlen) {
+            nr.fixed_vlen = nr.fixed_vlen_put; /* only PUTs came out */
+        }
         if (keep_inputs) {
             /* output is dropped at the end of the pass: pooled temporaries */
             nr.keys = e->talloc<uint8_t>(kbytes);
@@ -3189,7 +3262,7 @@ static int32_t compact_finish(HipEngine *e, rrdb_compact_stats *stats)
             HIP_OK(hipMalloc(&nr.sk, n_out * 8));
         }
         HIP_OK(hipEventRecord(ev[3], e->stream));
-        if (e->emit_mode == 2 || e->pend.fk || e->pend.no_rewrite) {
+        if (e->emit_mode == 2 || e->pend.chunked || e->pend.fk || e->pend.no_rewrite) {
             uint64_t *d_row_ksrc = e->talloc<uint64_t>(n_out * 8);
             uint64_t *d_row_vsrc = e->talloc<uint64_t>(n_out * 8);
             uint32_t *d_row_patch = e->talloc<uint32_t>(n_out * 4);
@@ -3232,9 +3305,11 @@ static int32_t compact_finish(HipEngine *e, rrdb_compact_stats *stats)
     } else {
         e->server_quit_sync(); /* the resident kernel holds the freed runs */
         e->invalidate_ctxs(); /* parked views reference the freed runs */
-        for (auto &r : e->runs)
-            e->free_run(r);
-        e->runs.clear();
+        /* only the window's runs go; the merged run takes their place at
+         * index `first`, older and newer runs stay where they are */
+        for (int r = 0; r < R; r++)
+            e->free_run(e->runs[first + r]);
+        e->runs.erase(e->runs.begin() + first, e->runs.begin() + first + R);
         if (n_out > 0) {
             uint64_t fo2[2], lo2[2];
             uint8_t h32[32], t32[32];
@@ -3248,7 +3323,7 @@ static int32_t compact_finish(HipEngine *e, rrdb_compact_stats *stats)
             e->build_tails(nr);
             e->build_meta(nr);
             e->build_bloom(nr);
-            e->runs.push_back(nr);
+            e->runs.insert(e->runs.begin() + first, nr);
         }
         e->d_runs_dirty = true;
         e->ldst_elig_cache = -1;
@@ -3284,6 +3359,81 @@ int32_t rrdb_manual_compact_finish(void *h, rrdb_compact_stats *stats)
     auto *e = (HipEngine *)h;
     std::lock_guard<std::mutex> g(e->mu);
     return compact_finish(e, stats);
+}
+
+/* ---- engine-only extensions (include/rrdb_engine_ext.h) ---- */
+
+/* window pass under the handle lock; the caller flushed and validated */
+static int32_t compact_window(HipEngine *e, size_t first, size_t n, uint32_t epoch_now,
+                              rrdb_compact_stats *stats)
+{
+    CompactWindow w{first, n};
+    int32_t rc = compact_begin(e, nullptr, epoch_now, &w);
+    if (rc != RRDB_OK) {
+        if (stats)
+            *stats = rrdb_compact_stats{};
+        return rc;
+    }
+    return compact_finish(e, stats);
+}
+
+int32_t rrdb_compact_runs(void *h, uint64_t first_run, uint64_t n_runs, uint32_t epoch_now,
+                          rrdb_compact_stats *stats)
+{
+    auto *e = (HipEngine *)h;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (stats)
+        *stats = rrdb_compact_stats{};
+    if (e->pend.active || e->manual_compact_disabled)
+        return RRDB_INVALID_ARGUMENT;
+    if (engine_flush(e) != RRDB_OK) /* as the manual pass: the memtable becomes a run */
+        return RRDB_IO_ERROR;
+    uint64_t R = e->runs.size();
+    if (n_runs == 0 || first_run >= R || n_runs > R - first_run)
+        return RRDB_INVALID_ARGUMENT;
+    return compact_window(e, (size_t)first_run, (size_t)n_runs, epoch_now, stats);
+}
+
+/* Size-tiered pick over the age-ordered run list: start from the two newest
+ * runs and extend the window towards older runs while the next older run is
+ * no more than twice the records gathered so far — a big old run is left
+ * alone until the young ones have grown to its tier. */
+int32_t rrdb_auto_compact(void *h, uint32_t epoch_now, uint64_t *first_run_out,
+                          uint64_t *n_runs_out, rrdb_compact_stats *stats)
+{
+    auto *e = (HipEngine *)h;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (stats)
+        *stats = rrdb_compact_stats{};
+    if (first_run_out)
+        *first_run_out = 0;
+    if (n_runs_out)
+        *n_runs_out = 0;
+    if (e->pend.active)
+        return RRDB_INVALID_ARGUMENT;
+    if (e->bulk_load)
+        return RRDB_OK;
+    if (e->runs.size() < e->l0_trigger)
+        return RRDB_OK;
+    /* the pass flushes first, as every pass does; pick over the result so
+     * the window still ends at the newest run */
+    if (engine_flush(e) != RRDB_OK)
+        return RRDB_IO_ERROR;
+    size_t R = e->runs.size();
+    size_t s = R - 2;
+    uint64_t acc = e->runs[R - 1].n + e->runs[R - 2].n;
+    while (s > 0 && e->runs[s - 1].n <= 2 * acc) {
+        s--;
+        acc += e->runs[s].n;
+    }
+    int32_t rc = compact_window(e, s, R - s, epoch_now, stats);
+    if (rc == RRDB_OK) {
+        if (first_run_out)
+            *first_run_out = s;
+        if (n_runs_out)
+            *n_runs_out = R - s;
+    }
+    return rc;
 }
 
 } /* extern "C" */

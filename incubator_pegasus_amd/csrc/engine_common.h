@@ -133,7 +133,16 @@ struct CompactParams {
     int32_t n_ops;
     const DevRule *rules; /* device */
     const uint8_t *pats;  /* device pattern blob */
+    /* 1 = no older run lies below the merged window (the full pass): dropped
+     * records vanish.  0 = window (minor) pass over runs [first>0, ..): a
+     * tombstone is kept verbatim and a PUT the filter removes is converted
+     * into a tombstone (changed[] == CH_TOMBSTONE), so the older version in
+     * a run outside the window stays hidden. */
+    uint8_t bottommost;
 };
+
+/* changed[] values written by the compaction rank kernels */
+enum { CH_NONE = 0, CH_REWRITE = 1, CH_TOMBSTONE = 2 };
 
 
 /* fused small-multi_get argument block (one-launch YCSB-E path) */

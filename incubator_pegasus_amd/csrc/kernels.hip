@@ -1028,10 +1028,10 @@ enum { D_NONE = 0, D_KEEP, D_SHADOWED, D_TOMBSTONE, D_EXPIRED, D_FILTERED };
  * Hot path reads only the 8B meta column ((expire<<32)|kind, built at run
  * creation) — key bytes are touched only under user rules / hash
  * validation, value bytes never (no rule inspects value data). */
-__device__ static int dev_disposition(const DevRun &r, uint64_t i, const CompactParams &cp,
-                                      int shadow, uint8_t *changed_out, uint32_t *new_ts_out,
-                                      uint64_t *kl_out, uint64_t *vl_out,
-                                      const uint64_t *mword = nullptr)
+__device__ static int dev_filter_disposition(const DevRun &r, uint64_t i, const CompactParams &cp,
+                                             int shadow, uint8_t *changed_out,
+                                             uint32_t *new_ts_out, uint64_t *kl_out,
+                                             uint64_t *vl_out, const uint64_t *mword)
 {
     *changed_out = 0;
     *new_ts_out = 0;
@@ -1143,6 +1143,39 @@ __device__ static int dev_disposition(const DevRun &r, uint64_t i, const Compact
     return D_KEEP;
 }
 
+/* Disposition under the pass's level.  Bottommost (cp.bottommost, the full
+ * pass): exactly the filter above.  Non-bottommost (a window with an older
+ * run below it) restates rocksdb's CompactionIterator: nothing but a
+ * shadowed version may disappear, since an older version of the key can sit
+ * in a run outside the window.  A tombstone is emitted verbatim; a PUT the
+ * filter removes (Decision::kRemove) is emitted as a tombstone — key copied,
+ * empty value, own seqno, kind bit set — flagged CH_TOMBSTONE for the emit. */
+__device__ static inline int dev_disposition(const DevRun &r, uint64_t i, const CompactParams &cp,
+                                             int shadow, uint8_t *changed_out,
+                                             uint32_t *new_ts_out, uint64_t *kl_out,
+                                             uint64_t *vl_out, const uint64_t *mword = nullptr)
+{
+    int disp = dev_filter_disposition(r, i, cp, shadow, changed_out, new_ts_out, kl_out, vl_out,
+                                      mword);
+    if (!cp.bottommost && disp >= D_TOMBSTONE) {
+        *kl_out = r.fixed_klen ? r.fixed_klen : (r.koff[i + 1] - r.koff[i]);
+        if (disp == D_TOMBSTONE) {
+            *vl_out = r.fixed_vlen ? r.fixed_vlen : (r.voff[i + 1] - r.voff[i]);
+        } else {
+            *vl_out = 0;
+            *changed_out = CH_TOMBSTONE;
+        }
+    }
+    return disp;
+}
+
+/* does a record with this disposition reach the output run? (0/1: feeds the
+ * keep prefix sum) */
+__device__ static inline uint64_t dev_emitted(int disp, const CompactParams &cp)
+{
+    return (disp == D_KEEP || (!cp.bottommost && disp >= D_TOMBSTONE)) ? 1 : 0;
+}
+
 /* fused rank + newest-wins + compaction filter: one pass over the input
  * records computes each record's merged position, shadow state and filter
  * disposition, writing keep/changed/new-expire/sizes scattered by rank.
@@ -1201,7 +1234,7 @@ __global__ void k_rank_compact(const DevRun *runs, int R, const uint64_t *lo, co
             uint64_t okl, ovl;
             disp = dev_disposition(runs[r], i, cp, shadow, &ch, &nts, &okl, &ovl);
             order[rank] = ((uint64_t)r << 40) | i;
-            keepw[rank] = (disp == D_KEEP) ? 1 : 0;
+            keepw[rank] = dev_emitted(disp, cp);
             if (changed)
                 changed[rank] = ch;
             if (new_expire)
@@ -1371,7 +1404,7 @@ __global__ void __launch_bounds__(BLOCK) k_rank_compact_ldst(
         uint64_t okl, ovl;
         disp = dev_disposition(runs[r], i, cp, shadow, &ch, &nts, &okl, &ovl);
         order[rank] = ((uint64_t)r << 40) | i;
-        keepw[rank] = (disp == D_KEEP) ? 1 : 0;
+        keepw[rank] = dev_emitted(disp, cp);
         if (changed)
             changed[rank] = ch;
         if (new_expire)
@@ -1611,7 +1644,7 @@ __device__ static inline int grp_epilogue(const DevRun *runs, int q, uint64_t i,
     uint32_t nts;
     uint64_t okl, ovl;
     int disp = dev_disposition(runs[q], i, cp, shadow, &ch, &nts, &okl, &ovl, smeta);
-    keepw[rank] = (disp == D_KEEP) ? 1 : 0;
+    keepw[rank] = dev_emitted(disp, cp);
     if (changed)
         changed[rank] = ch;
     if (new_expire)
@@ -2046,8 +2079,10 @@ __global__ void k_compact_gather_meta(const DevRun *runs, const uint64_t *order,
         /* input offsets stay voff-addressed: tombstones make input value
          * strides irregular even when every PUT shares one length */
         row_vsrc[o] = (uint64_t)(r.vals + r.voff[i]);
-        row_patch[o] = (changed && changed[p]) ? 3 : 0;
-        osk[o] = r.sk[i];
+        row_patch[o] = (changed && changed[p] == CH_REWRITE) ? 3 : 0;
+        /* a filter-removed PUT of a non-bottommost pass leaves as a tombstone:
+         * same seqno, kind bit set (its value row is empty via vsz == 0) */
+        osk[o] = r.sk[i] | ((changed && changed[p] == CH_TOMBSTONE) ? 1ull : 0ull);
         if (o == n_out - 1) {
             row_koff[n_out] = kbytes;
             row_voff[n_out] = vbytes;
@@ -2066,7 +2101,7 @@ __global__ void k_compact_gather_expire(const uint64_t *keepw, const uint64_t *k
          p += gridDim.x * (uint64_t)blockDim.x) {
         if (!keepw[p])
             continue;
-        row_expire[kpos[p]] = changed[p] ? new_expire[p] : 0xFFFFFFFFu;
+        row_expire[kpos[p]] = (changed[p] == CH_REWRITE) ? new_expire[p] : 0xFFFFFFFFu;
     }
 }
 
@@ -3231,7 +3266,7 @@ __global__ void __launch_bounds__(LRK_BLK, 1) k_rank_compact_lds(
         uint64_t okl, ovl;
         disp = dev_disposition(runs[r], i, cp, shadow, &ch, &nts, &okl, &ovl);
         order[rank] = ((uint64_t)r << 40) | i;
-        keepw[rank] = (disp == D_KEEP) ? 1 : 0;
+        keepw[rank] = dev_emitted(disp, cp);
         if (changed)
             changed[rank] = ch;
         if (new_expire)
