@@ -333,7 +333,9 @@ const char *rrdb_backend(void);
  * events on the engine's own stream (bench/roofline introspection; the CPU
  * oracle returns -1).  Phases: "compact_rank", "compact_flags",
  * "compact_emit", "compact_total", "scan_state", "scan_emit", "get_search",
- * "view_rank".  Returns -1 if never recorded. */
+ * "view_rank", and, on the parent handle of a partition split (rrdb_engine_ext.h),
+ * "split_classify", "split_emit", "split_total".  Returns -1 if never
+ * recorded. */
 double rrdb_phase_ms(void *h, const char *phase);
 
 #ifdef __cplusplus

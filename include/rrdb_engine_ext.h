@@ -28,6 +28,49 @@
  * (none is dropped), expired/filtered count the conversions, output_records
  * counts every emitted record (tombstones included), and
  * input_records == output_records + shadowed.
+ *
+ * Partition split.  The table's partition count doubles from N to 2N; every
+ * partition p gives rise to child p + N, and from then on a record belongs to
+ * the handle whose index equals pegasus_key_hash(key) & (2N-1).  The reference
+ * copies the parent's checkpoint into the child's directory
+ * (replica_split_manager.cpp:278, copy_checkpoint_to_dir), sets
+ * partition_version = 2N-1 on both replicas (set_partition_version, :884), and
+ * leaves the foreign half to the compaction filter's stale-split-hash rule
+ * (key_ttl_compaction_filter.h:114-121) at some later compaction.  With runs
+ * resident in HBM that route holds the partition twice until both sides have
+ * compacted.  rrdb_split does the data part on the device instead: each
+ * record is classified by its hash and each run is cut, stably, into the part
+ * the parent keeps and the part the child receives.
+ *   - Ownership: with mask = new_partition_count - 1 and
+ *     t = key_hash(key) & mask, the record goes to the parent if
+ *     t == parent.pidx, to the child if t == child.pidx, nowhere otherwise
+ *     (it was stale before the split).  The hash is the compaction filter's
+ *     and the scan validation's: over the hashkey, or over the sortkey bytes
+ *     when the hashkey is empty.  A key shorter than two bytes (the codec
+ *     produces none) stays in the parent.
+ *   - All versions of a key share a hash, so tombstones, shadowed versions
+ *     and expired records travel with their key.  Nothing is merged,
+ *     filtered, rewritten or expired: records move byte for byte with their
+ *     seq_kind, and there is no epoch_now argument.
+ *   - Every parent run is partitioned stably (key order kept) and run order
+ *     is kept on both sides.  A run that contributes nothing to a side
+ *     produces no run there.  The parent's memtable is flushed first.
+ *   - Device memory, two phases.  A: all child runs are built with the
+ *     parent untouched; a failed allocation frees them and returns kIOError
+ *     with both handles as before.  B: the parent is pruned one run at a time
+ *     (allocate the kept part, emit, free the source, swap); a failed
+ *     allocation here leaves the remaining runs whole, counts those that
+ *     still hold foreign records in parent_unpruned_runs and returns kOk: the
+ *     child is complete and the leftovers are exactly the stale records the
+ *     compaction filter drops.  Peak residency is about 1.5x the partition
+ *     plus half the largest run, ending at 1x.  A run that is entirely the
+ *     parent's is not rewritten.
+ *   - After kOk both handles have partition_version = new_partition_count-1,
+ *     the child's sequence floor equals the parent's (later writes to the
+ *     child outrank everything it inherited), and the parent's parked scan
+ *     contexts are reclaimed as after a compaction (scan_next: kNotFound).
+ *   - rrdb_phase_ms(parent, ...) reports split_classify, split_emit and
+ *     split_total.
  */
 #ifndef RRDB_ENGINE_EXT_H
 #define RRDB_ENGINE_EXT_H
@@ -61,6 +104,34 @@ int32_t rrdb_compact_runs(void *h, uint64_t first_run, uint64_t n_runs,
  * flushed first and the new run is part of the pick. */
 int32_t rrdb_auto_compact(void *h, uint32_t epoch_now, uint64_t *first_run_out,
                           uint64_t *n_runs_out, rrdb_compact_stats *stats);
+
+/* Split-time counters.  On the normal path parent_records + child_records +
+ * dropped_records == input_records; a run left whole (parent_unpruned_runs)
+ * counts all its records and bytes on the parent side. */
+typedef struct {
+    uint64_t input_records;   /* records in the parent's runs before the split   */
+    uint64_t parent_records;  /* records left in the parent                      */
+    uint64_t child_records;   /* records moved to the child                      */
+    uint64_t dropped_records; /* records owned by neither (already stale)        */
+    uint64_t parent_bytes;    /* key+value bytes, parent side                    */
+    uint64_t child_bytes;     /* key+value bytes, child side                     */
+    uint64_t runs_in, parent_runs, child_runs;
+    uint64_t parent_unpruned_runs; /* phase B ran out of memory; 0 normally      */
+} rrdb_split_stats;
+
+/* Split `parent` (partition p of N) into itself and `child` (p + N), with
+ * new_partition_count = 2N; see the header comment.  The child must be an
+ * empty handle on the same device.  kInvalidArgument, both handles unchanged:
+ * new_partition_count not a power of two in [2, 2^30];
+ * parent.pidx >= new_partition_count/2;
+ * child.pidx != parent.pidx + new_partition_count/2; parent == child; app_id,
+ * device or data_version differ; the child has runs, memtable entries or
+ * parked scan contexts; a split compaction or a pipelined count scan is
+ * pending on either handle.  manual_compact.disabled does not stop a split.
+ * Both handles' locks are taken together (deadlock-free); all device work
+ * runs on the parent's stream. */
+int32_t rrdb_split(void *parent, void *child, int32_t new_partition_count,
+                   rrdb_split_stats *stats);
 
 #ifdef __cplusplus
 }

@@ -117,6 +117,21 @@ class _CompactStats(C.Structure):
     ]
 
 
+class _SplitStats(C.Structure):
+    _fields_ = [
+        ("input_records", C.c_uint64),
+        ("parent_records", C.c_uint64),
+        ("child_records", C.c_uint64),
+        ("dropped_records", C.c_uint64),
+        ("parent_bytes", C.c_uint64),
+        ("child_bytes", C.c_uint64),
+        ("runs_in", C.c_uint64),
+        ("parent_runs", C.c_uint64),
+        ("child_runs", C.c_uint64),
+        ("parent_unpruned_runs", C.c_uint64),
+    ]
+
+
 def _cslice(b: bytes, keep: list) -> _CSlice:
     """Build a _CSlice over a copy of b; the backing buffer is appended to
     `keep`, which the caller must hold alive across the C call (struct field
@@ -154,6 +169,20 @@ class CompactStats:
     tombstones: int = 0
     shadowed: int = 0
     output_bytes: int = 0
+
+
+@dataclass
+class SplitStats:
+    input_records: int = 0
+    parent_records: int = 0
+    child_records: int = 0
+    dropped_records: int = 0
+    parent_bytes: int = 0
+    child_bytes: int = 0
+    runs_in: int = 0
+    parent_runs: int = 0
+    child_runs: int = 0
+    parent_unpruned_runs: int = 0
 
 
 class RrdbLib:
@@ -238,6 +267,11 @@ class RrdbLib:
             L.rrdb_auto_compact.argtypes = [
                 C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                 C.POINTER(_CompactStats)]
+        self.has_split = hasattr(L, "rrdb_split")
+        if self.has_split:
+            L.rrdb_split.restype = C.c_int32
+            L.rrdb_split.argtypes = [
+                C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(_SplitStats)]
 
     @property
     def backend(self) -> str:
@@ -623,3 +657,19 @@ class RrdbPartition:
                                         C.byref(st))
         stats = CompactStats(**{f[0]: getattr(st, f[0]) for f in _CompactStats._fields_})
         return err, first.value, n.value, stats
+
+    # ---- partition split: engine-only (include/rrdb_engine_ext.h) ----
+    def split(self, child: "RrdbPartition", new_partition_count: int):
+        """Split this partition (p of N) on the device into itself and `child`
+        (p + N, an empty handle on the same GPU), new_partition_count = 2N.
+        Returns (err, SplitStats), like manual_compact."""
+        if not self.lib.has_split:
+            raise RuntimeError(
+                f"split: backend {self.lib.backend!r} ({self.lib.path}) does not export "
+                "rrdb_split (engine-only extension)")
+        if child.lib is not self.lib:
+            raise RuntimeError("split: parent and child must come from the same library")
+        st = _SplitStats()
+        err = self._L.rrdb_split(self._h, child._h, new_partition_count, C.byref(st))
+        stats = SplitStats(**{f[0]: getattr(st, f[0]) for f in _SplitStats._fields_})
+        return err, stats

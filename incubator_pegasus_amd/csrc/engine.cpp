@@ -119,6 +119,19 @@ void launch_emit_compact(const DevRun *, const uint64_t *, uint64_t, const uint6
                          const uint64_t *, uint32_t, uint8_t *, uint8_t *, uint64_t *, uint64_t *,
                          uint64_t *, uint64_t, hipStream_t);
 
+void launch_split_classify(const uint8_t *, const uint64_t *, uint64_t, const uint64_t *, uint64_t,
+                           uint64_t, uint64_t, uint64_t, uint8_t *, uint64_t *, uint32_t *, int,
+                           hipStream_t);
+void launch_split_sizes(const uint8_t *, uint32_t, const uint64_t *, const uint64_t *, uint64_t,
+                        uint64_t *, uint64_t *, hipStream_t);
+void launch_split_scatter(const uint8_t *, const uint64_t *, const uint8_t *, const uint64_t *,
+                          const uint64_t *, uint64_t, uint64_t, uint64_t, const uint8_t *,
+                          uint32_t, const uint64_t *, uint64_t, const uint64_t *,
+                          const uint64_t *, uint64_t, uint64_t, uint64_t, uint64_t *, uint64_t *,
+                          uint64_t *, uint64_t *, uint64_t *, hipStream_t);
+void launch_split_copy(const uint64_t *, const uint64_t *, uint64_t, uint64_t, uint64_t,
+                       uint64_t *, uint8_t *, hipStream_t);
+
 #define HIP_OK(x)                                                                                  \
     do {                                                                                           \
         hipError_t e_ = (x);                                                                       \
@@ -886,6 +899,10 @@ struct HipEngine {
                           0 = global searches + bound-table narrowing,
                           1 = LDS-staged full-key block rank
                           (env "engine.rank_mode": grp|ldst|global|lds) */
+    int split_crc_lds = 1; /* rrdb_split classify: crc64 table staged in LDS
+                              once per workgroup (1, default) or read from
+                              global memory (0) (env "engine.split_crc":
+                              lds|global; DESIGN.md §3c has the A/B) */
     int bt_shift = 5;  /* bound-table block = 1<<bt_shift records (env
                           "engine.bt_shift") */
     int grp_blocks = 3584; /* group-rank grid cap (env "engine.grp_blocks");
@@ -967,37 +984,55 @@ struct HipEngine {
         r = RunBuf();
     }
 
+    /* the three run-column builders below abort on a full device, like every
+     * HIP_OK; with try_alloc they return false instead (the split unwinds) */
+    bool col_alloc(uint64_t **p, uint64_t bytes, bool try_alloc)
+    {
+        if (!try_alloc) {
+            HIP_OK(hipMalloc(p, bytes));
+            return true;
+        }
+        return hipMalloc(p, bytes) == hipSuccess;
+    }
     /* packed 8B-strided probe words for the single-word search mode */
-    void build_tails(RunBuf &r)
+    bool build_tails(RunBuf &r, bool try_alloc = false)
     {
         if (r.n == 0 || r.fixed_klen < 8 || r.lcp_exact + 8 < r.fixed_klen)
-            return;
-        HIP_OK(hipMalloc(&r.tails, r.n * 8));
+            return true;
+        if (!col_alloc(&r.tails, r.n * 8, try_alloc))
+            return false;
         launch_build_tails(r.keys, r.fixed_klen, r.n, r.tails, stream);
         HIP_OK(hipStreamSynchronize(stream));
+        return true;
     }
 
     /* disposition column (expire<<32|kind): one 8B gather replaces the
      * sk + voff + value-header chain in filter/scan-state evaluation */
-    void build_meta(RunBuf &r)
+    bool build_meta(RunBuf &r, bool try_alloc = false)
     {
         if (r.n == 0)
-            return;
-        HIP_OK(hipMalloc(&r.meta, r.n * 8));
+            return true;
+        if (!col_alloc(&r.meta, r.n * 8, try_alloc))
+            return false;
         launch_build_meta(r.vals, r.voff, r.fixed_vlen, r.sk, r.n, data_version, r.meta,
                           stream);
         HIP_OK(hipStreamSynchronize(stream));
+        return true;
     }
 
     /* §8(f)3: ~10 bits/key blocked bloom, built once per run on device */
-    void build_bloom(RunBuf &r)
+    /* want: -1 = this handle's rocksdb.filter_type, else 0/1 (the split
+     * builds the child's runs and applies the child's setting) */
+    bool build_bloom(RunBuf &r, bool try_alloc = false, int want = -1)
     {
-        if (!bloom_enabled || r.n == 0)
-            return;
+        if (!(want < 0 ? bloom_enabled : want != 0) || r.n == 0)
+            return true;
         uint64_t n_blocks = (r.n * 10 + 511) / 512;
         if (n_blocks == 0)
             n_blocks = 1;
-        HIP_OK(hipMalloc(&r.bloom, n_blocks * 64));
+        if (!col_alloc(&r.bloom, n_blocks * 64, try_alloc) ||
+            !col_alloc(&r.pfx_bloom, n_blocks * 64, try_alloc))
+            return false;
         HIP_OK(hipMemsetAsync(r.bloom, 0, n_blocks * 64, stream));
         DevRun dr{};
         dr.keys = r.keys;
@@ -1009,12 +1044,12 @@ struct HipEngine {
         launch_bloom_build(dr, r.bloom, n_blocks, stream);
         /* §8(f)3 second half: hashkey-prefix bloom (the reference's
          * prefix-extractor filter, _init.cpp:816-841, hashkey_transform.h) */
-        HIP_OK(hipMalloc(&r.pfx_bloom, n_blocks * 64));
         HIP_OK(hipMemsetAsync(r.pfx_bloom, 0, n_blocks * 64, stream));
         launch_bloom_pfx_build(dr, r.pfx_bloom, n_blocks, stream);
         HIP_OK(hipStreamSynchronize(stream));
         r.bloom_blocks = n_blocks;
         r.pfx_bloom_blocks = n_blocks;
+        return true;
     }
 
     DevRun *dev_runs()
@@ -1620,6 +1655,8 @@ int32_t rrdb_set_envs(void *h, const char *const *keys, const char *const *value
                 (void)hipGraphExecDestroy(e->mg_graph);
                 e->mg_graph = nullptr;
             }
+        } else if (k == "engine.split_crc") {
+            e->split_crc_lds = (v == "global") ? 0 : 1;
         } else if (k == "engine.emit_mode") {
             e->emit_mode = (v == "input") ? 1 : (v == "rank" ? 0 : 2);
         } else if (k == "engine.l0_compaction_trigger") {
@@ -3434,6 +3471,302 @@ int32_t rrdb_auto_compact(void *h, uint32_t epoch_now, uint64_t *first_run_out,
             *n_runs_out = R - s;
     }
     return rc;
+}
+
+/* ---- partition split (rrdb_split) ----
+ * Per source run: one classify pass writes side[] and per-wave side counts,
+ * one scan over the counts gives wave bases; a side is then emitted by
+ * split_emit_side.  Temporaries are arena memory sized for the largest run
+ * and reused run after run (everything is ordered on the parent's stream). */
+struct SplitRunInfo {
+    uint8_t *side = nullptr;   /* [n] SPLIT_* code per record */
+    uint64_t *wbase = nullptr; /* scanned [parent waves | child waves] counts */
+    uint64_t nw = 0;
+    uint64_t cnt[2] = {0, 0};  /* records owned by parent / child */
+    bool has_put[2] = {false, false};
+};
+struct SplitTmp {
+    uint64_t *ksz = nullptr, *kpos = nullptr, *vsz = nullptr, *vpos = nullptr;
+    uint64_t *row_ksrc = nullptr, *row_vsrc = nullptr, *kanch = nullptr, *vanch = nullptr;
+    uint64_t *psc_k = nullptr, *psc_v = nullptr;
+    hipEvent_t ev[2] = {};
+    double emit_ms = 0.0;
+};
+
+/* first/last key -> set_pfx, then the tails / meta / bloom columns, as every
+ * run-creation path does.  false = the device is full (caller frees r). */
+static bool split_finish_run(HipEngine *e, RunBuf &r, bool bloom)
+{
+    uint64_t fo2[2], lo2[2];
+    uint8_t h32[32], t32[32];
+    HIP_OK(hipMemcpy(fo2, r.koff, 16, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(lo2, r.koff + (r.n - 1), 16, hipMemcpyDeviceToHost));
+    uint64_t fl = std::min<uint64_t>(fo2[1] - fo2[0], 32);
+    uint64_t ll = std::min<uint64_t>(lo2[1] - lo2[0], 32);
+    HIP_OK(hipMemcpy(h32, r.keys + fo2[0], fl ? fl : 1, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(t32, r.keys + lo2[0], ll ? ll : 1, hipMemcpyDeviceToHost));
+    set_pfx(lcp_exact32(h32, fl, t32, ll), &r.pfx_skip, &r.lcp_exact);
+    return e->build_tails(r, true) && e->build_meta(r, true) &&
+           e->build_bloom(r, true, bloom ? 1 : 0);
+}
+
+/* Build side s (0 parent, 1 child) of `src` as a finished run in *out and
+ * its key+value bytes in *bytes.  si.cnt[s] > 0.  false = an allocation
+ * failed; nothing is left allocated and src is untouched. */
+static bool split_emit_side(HipEngine *e, const RunBuf &src, const SplitRunInfo &si, int s,
+                            SplitTmp &t, bool bloom, RunBuf *out, uint64_t *bytes)
+{
+    const uint64_t ns = si.cnt[s], n = src.n;
+    const uint64_t fk = src.fixed_klen, fv = src.fixed_vlen;
+    uint64_t kbytes = ns * fk, vbytes = ns * fv;
+    if (!fk || !fv) {
+        /* variable-length column: scan this side's sizes for its offsets */
+        uint64_t tot[4] = {0, 0, 0, 0};
+        launch_split_sizes(si.side, (uint32_t)s, src.koff, src.voff, n, fk ? nullptr : t.ksz,
+                           fv ? nullptr : t.vsz, e->stream);
+        if (!fk) {
+            launch_psum(t.ksz, t.kpos, n, t.psc_k, e->stream);
+            HIP_OK(hipMemcpyAsync(&tot[0], t.kpos + n - 1, 8, hipMemcpyDeviceToHost, e->stream));
+            HIP_OK(hipMemcpyAsync(&tot[1], t.ksz + n - 1, 8, hipMemcpyDeviceToHost, e->stream));
+        }
+        if (!fv) {
+            launch_psum(t.vsz, t.vpos, n, t.psc_v, e->stream);
+            HIP_OK(hipMemcpyAsync(&tot[2], t.vpos + n - 1, 8, hipMemcpyDeviceToHost, e->stream));
+            HIP_OK(hipMemcpyAsync(&tot[3], t.vsz + n - 1, 8, hipMemcpyDeviceToHost, e->stream));
+        }
+        HIP_OK(hipStreamSynchronize(e->stream));
+        if (!fk)
+            kbytes = tot[0] + tot[1];
+        if (!fv)
+            vbytes = tot[2] + tot[3];
+    }
+    RunBuf r;
+    r.n = ns;
+    if (hipMalloc(&r.keys, kbytes ? kbytes : 1) != hipSuccess ||
+        hipMalloc(&r.vals, vbytes ? vbytes : 1) != hipSuccess ||
+        hipMalloc(&r.koff, (ns + 1) * 8) != hipSuccess ||
+        hipMalloc(&r.voff, (ns + 1) * 8) != hipSuccess ||
+        hipMalloc(&r.sk, ns * 8) != hipSuccess) {
+        (void)hipGetLastError();
+        e->free_run(r);
+        return false;
+    }
+    HIP_OK(hipEventRecord(t.ev[0], e->stream));
+    launch_split_scatter(src.keys, src.koff, src.vals, src.voff, src.sk, n, fk, fv, si.side,
+                         (uint32_t)s, si.wbase + (s ? si.nw : 0), s ? si.cnt[0] : 0, t.kpos,
+                         t.vpos, ns, kbytes, vbytes, r.koff, r.voff, r.sk, t.row_ksrc,
+                         t.row_vsrc, e->stream);
+    launch_split_copy(t.row_ksrc, r.koff, ns, fk, kbytes, t.kanch, r.keys, e->stream);
+    launch_split_copy(t.row_vsrc, r.voff, ns, fv, vbytes, t.vanch, r.vals, e->stream);
+    HIP_OK(hipEventRecord(t.ev[1], e->stream));
+    HIP_OK(hipStreamSynchronize(e->stream));
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, t.ev[0], t.ev[1]) == hipSuccess)
+        t.emit_ms += ms;
+    /* a subset of a fixed-stride run is fixed-stride.  The put-stride is
+     * "the length every PUT shares" and is 0 for a run without PUTs
+     * (detect_fixed_vlen_put), so it is inherited only when the side has one */
+    r.fixed_klen = src.fixed_klen;
+    r.fixed_vlen = src.fixed_vlen;
+    r.fixed_vlen_put = si.has_put[s] ? src.fixed_vlen_put : 0;
+    if (!split_finish_run(e, r, bloom)) {
+        (void)hipGetLastError();
+        e->free_run(r);
+        return false;
+    }
+    *out = r;
+    *bytes = kbytes + vbytes;
+    return true;
+}
+
+int32_t rrdb_split(void *parent, void *child, int32_t new_partition_count,
+                   rrdb_split_stats *stats)
+{
+    if (stats)
+        *stats = rrdb_split_stats{};
+    if (!parent || !child || parent == child)
+        return RRDB_INVALID_ARGUMENT;
+    auto *p = (HipEngine *)parent, *c = (HipEngine *)child;
+    /* std::scoped_lock takes both mutexes with the deadlock-avoiding
+     * std::lock, so two threads splitting (a,b) and (b,a) cannot deadlock */
+    std::scoped_lock g(p->mu, c->mu);
+    const int64_t npc = new_partition_count;
+    if (npc < 2 || npc > (1ll << 30) || (npc & (npc - 1)) != 0)
+        return RRDB_INVALID_ARGUMENT;
+    if (p->pidx < 0 || p->pidx >= npc / 2 || c->pidx != p->pidx + npc / 2)
+        return RRDB_INVALID_ARGUMENT;
+    if (p->app_id != c->app_id || p->device != c->device || p->data_version != c->data_version)
+        return RRDB_INVALID_ARGUMENT;
+    if (!c->runs.empty() || !c->memtable.empty() || !c->ctxs.empty())
+        return RRDB_INVALID_ARGUMENT;
+    if (p->pend.active || c->pend.active || p->pend_scan.active || c->pend_scan.active)
+        return RRDB_INVALID_ARGUMENT;
+    p->activate();
+    if (engine_flush(p) != RRDB_OK) /* as the compaction entry points */
+        return RRDB_IO_ERROR;
+    p->scratch_reset();
+    rrdb_split_stats st{};
+    const size_t R = p->runs.size();
+    st.runs_in = R;
+    uint64_t maxn = 0, max_kb = 0, max_vb = 0;
+    bool any_var = false;
+    for (auto &r : p->runs) {
+        st.input_records += r.n;
+        maxn = std::max(maxn, r.n);
+        any_var = any_var || !r.fixed_klen || !r.fixed_vlen;
+    }
+    /* byte size of every run (koff[n] + voff[n]): stats for runs left whole,
+     * and the anchor scratch of the variable-length copies */
+    std::vector<uint64_t> run_kb(R, 0), run_vb(R, 0);
+    for (size_t i = 0; i < R; i++) {
+        const RunBuf &r = p->runs[i];
+        HIP_OK(hipMemcpy(&run_kb[i], r.koff + r.n, 8, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(&run_vb[i], r.voff + r.n, 8, hipMemcpyDeviceToHost));
+        max_kb = std::max(max_kb, run_kb[i]);
+        max_vb = std::max(max_vb, run_vb[i]);
+    }
+    hipEvent_t ev[4];
+    for (auto &x : ev)
+        HIP_OK(hipEventCreate(&x));
+    SplitTmp t;
+    HIP_OK(hipEventCreate(&t.ev[0]));
+    HIP_OK(hipEventCreate(&t.ev[1]));
+    auto drop_events = [&] {
+        for (auto &x : ev)
+            (void)hipEventDestroy(x);
+        (void)hipEventDestroy(t.ev[0]);
+        (void)hipEventDestroy(t.ev[1]);
+    };
+    HIP_OK(hipEventRecord(ev[0], p->stream));
+
+    /* classify + rank every run; one sync for all the counts */
+    std::vector<SplitRunInfo> info(R);
+    const uint64_t mask = (uint64_t)npc - 1;
+    uint64_t *h_cnt = (uint64_t *)p->pinned_buf((R ? R : 1) * 4 * 8);
+    HIP_OK(hipEventRecord(ev[1], p->stream));
+    for (size_t i = 0; i < R; i++) {
+        const RunBuf &r = p->runs[i];
+        SplitRunInfo &si = info[i];
+        if (r.n == 0)
+            continue;
+        si.nw = (r.n + 63) / 64;
+        si.side = p->talloc<uint8_t>(r.n);
+        uint64_t *d_wcnt = p->talloc<uint64_t>(2 * si.nw * 8);
+        si.wbase = p->talloc<uint64_t>(2 * si.nw * 8);
+        uint32_t *d_has_put = p->talloc<uint32_t>(8);
+        HIP_OK(hipMemsetAsync(d_has_put, 0, 8, p->stream));
+        launch_split_classify(r.keys, r.koff, r.fixed_klen, r.sk, r.n, mask, (uint64_t)p->pidx,
+                              (uint64_t)c->pidx, si.side, d_wcnt, d_has_put, p->split_crc_lds,
+                              p->stream);
+        launch_psum(d_wcnt, si.wbase, 2 * si.nw, p->psum_scratch(2 * si.nw), p->stream);
+        /* parent total = scan value where the child section starts */
+        HIP_OK(hipMemcpyAsync(&h_cnt[4 * i + 0], si.wbase + si.nw, 8, hipMemcpyDeviceToHost,
+                              p->stream));
+        HIP_OK(hipMemcpyAsync(&h_cnt[4 * i + 1], si.wbase + 2 * si.nw - 1, 8,
+                              hipMemcpyDeviceToHost, p->stream));
+        HIP_OK(hipMemcpyAsync(&h_cnt[4 * i + 2], d_wcnt + 2 * si.nw - 1, 8,
+                              hipMemcpyDeviceToHost, p->stream));
+        HIP_OK(hipMemcpyAsync(&h_cnt[4 * i + 3], d_has_put, 8, hipMemcpyDeviceToHost,
+                              p->stream));
+    }
+    HIP_OK(hipEventRecord(ev[2], p->stream));
+    HIP_OK(hipStreamSynchronize(p->stream));
+    for (size_t i = 0; i < R; i++) {
+        SplitRunInfo &si = info[i];
+        if (p->runs[i].n == 0)
+            continue;
+        si.cnt[0] = h_cnt[4 * i + 0];
+        si.cnt[1] = h_cnt[4 * i + 1] + h_cnt[4 * i + 2] - si.cnt[0];
+        si.has_put[0] = (uint32_t)h_cnt[4 * i + 3] != 0;
+        si.has_put[1] = (uint32_t)(h_cnt[4 * i + 3] >> 32) != 0;
+        st.child_records += si.cnt[1];
+        st.dropped_records += p->runs[i].n - si.cnt[0] - si.cnt[1];
+    }
+    t.row_ksrc = p->talloc<uint64_t>(maxn * 8);
+    t.row_vsrc = p->talloc<uint64_t>(maxn * 8);
+    if (any_var) {
+        t.ksz = p->talloc<uint64_t>(maxn * 8);
+        t.kpos = p->talloc<uint64_t>(maxn * 8);
+        t.vsz = p->talloc<uint64_t>(maxn * 8);
+        t.vpos = p->talloc<uint64_t>(maxn * 8);
+        t.psc_k = p->psum_scratch(maxn);
+        t.psc_v = p->psum_scratch(maxn);
+        t.kanch = p->talloc<uint64_t>((((max_kb + 15) >> 10) + 2) * 8);
+        t.vanch = p->talloc<uint64_t>((((max_vb + 15) >> 10) + 2) * 8);
+    }
+
+    /* phase A: every child run, the parent untouched */
+    std::vector<RunBuf> child_runs;
+    for (size_t i = 0; i < R; i++) {
+        if (info[i].cnt[1] == 0)
+            continue; /* the engine never holds an empty run */
+        RunBuf nr;
+        uint64_t b = 0;
+        if (!split_emit_side(p, p->runs[i], info[i], 1, t, c->bloom_enabled, &nr, &b)) {
+            for (auto &r : child_runs)
+                p->free_run(r);
+            drop_events();
+            return RRDB_IO_ERROR; /* both handles as before */
+        }
+        child_runs.push_back(nr);
+        st.child_bytes += b;
+    }
+
+    /* phase B: prune the parent run by run.  From here the parent's run list
+     * changes: retire its resident kernel and parked views first. */
+    p->server_quit_sync();
+    p->invalidate_ctxs();
+    std::vector<RunBuf> parent_runs;
+    bool full = false;
+    for (size_t i = 0; i < R; i++) {
+        RunBuf &src = p->runs[i];
+        const uint64_t np = info[i].cnt[0];
+        if (np == 0) {
+            p->free_run(src);
+            continue;
+        }
+        RunBuf nr;
+        uint64_t b = 0;
+        if (np != src.n && !full)
+            full = !split_emit_side(p, src, info[i], 0, t, p->bloom_enabled, &nr, &b);
+        if (np == src.n || full) {
+            /* nothing foreign in it, or the device is full: the run stays
+             * whole (its foreign records are what the compaction filter's
+             * stale-split-hash rule drops later) */
+            if (np != src.n)
+                st.parent_unpruned_runs++;
+            st.parent_records += src.n;
+            st.parent_bytes += run_kb[i] + run_vb[i];
+            parent_runs.push_back(src);
+            continue;
+        }
+        p->free_run(src);
+        parent_runs.push_back(nr);
+        st.parent_records += np;
+        st.parent_bytes += b;
+    }
+    HIP_OK(hipEventRecord(ev[3], p->stream));
+    HIP_OK(hipStreamSynchronize(p->stream));
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, ev[1], ev[2]) == hipSuccess)
+        p->phase_ms["split_classify"] = ms;
+    p->phase_ms["split_emit"] = t.emit_ms;
+    if (hipEventElapsedTime(&ms, ev[0], ev[3]) == hipSuccess)
+        p->phase_ms["split_total"] = ms;
+    drop_events();
+
+    p->runs = parent_runs;
+    c->runs = child_runs;
+    st.parent_runs = p->runs.size();
+    st.child_runs = c->runs.size();
+    p->partition_version = c->partition_version = (int32_t)(npc - 1);
+    /* later writes to the child outrank everything it inherited */
+    c->next_seq_floor = p->next_seq_floor;
+    p->d_runs_dirty = c->d_runs_dirty = true;
+    p->ldst_elig_cache = c->ldst_elig_cache = -1;
+    if (stats)
+        *stats = st;
+    return RRDB_OK;
 }
 
 } /* extern "C" */

@@ -28,6 +28,8 @@
  *    1-workgroup server (bounded 2ms idle exit) remove the per-call
  *    dispatch cost
  *  - crc64 table lives in __device__ memory (L1/L2-resident after first use)
+ *  - partition split (end of file): hash-classify with per-wave ballot
+ *    counts, one scan over n/32 words, scatter + the emit's chunk copies
  *  - integer/byte work only: HBM-bound, no MFMA by design
  */
 #include <hip/hip_runtime.h>
@@ -3403,4 +3405,205 @@ void launch_bloom_pfx_build(const DevRun &run, uint64_t *d_bloom, uint64_t n_blo
                             hipStream_t s)
 {
     k_bloom_pfx_build<<<grid_for(run.n, BLOCK), BLOCK, 0, s>>>(run, d_bloom, n_blocks);
+}
+
+/* ================= partition split (rrdb_split) =================
+ * One source run is cut into the records a side owns, in three steps:
+ *   classify: one record per lane, side = dev_key_hash(key) & mask compared
+ *             with the two partition indices; per-wave side counts come from
+ *             ballots, so ranking needs a scan over n/64 words only;
+ *   rank:     launch_psum over the [parent waves | child waves] count array;
+ *   emit:     scatter sk / offsets / source addresses by rank, then the
+ *             compaction emit's chunk-copy kernels move the bytes.
+ * Stable by construction: rank = wave base + lanes below me on my side. */
+enum { SPLIT_PARENT = 0, SPLIT_CHILD = 1, SPLIT_NONE = 2, SPLIT_OOB = 3 };
+
+/* crc64 with the table either in LDS (staged once per workgroup) or in
+ * global memory; key bytes are fetched a u64 at a time */
+template <bool LDS_TAB>
+__device__ static inline uint64_t split_crc64(const uint64_t *ltab, const uint8_t *p, uint64_t n)
+{
+    uint64_t crc = ~0ull;
+    uint64_t i = 0;
+    for (; i + 8 <= n; i += 8) {
+        uint64_t w;
+        __builtin_memcpy(&w, p + i, 8);
+        for (int j = 0; j < 8; j++) {
+            uint32_t idx = (uint8_t)(crc ^ w);
+            crc = (LDS_TAB ? ltab[idx] : d_crc64_table[idx]) ^ (crc >> 8);
+            w >>= 8;
+        }
+    }
+    for (; i < n; i++) {
+        uint32_t idx = (uint8_t)(crc ^ p[i]);
+        crc = (LDS_TAB ? ltab[idx] : d_crc64_table[idx]) ^ (crc >> 8);
+    }
+    return ~crc;
+}
+
+/* side[i] for every record; wcnt[w] / wcnt[nw + w] = parent / child records
+ * of wave-tile w (records [64w, 64w+64)); has_put[s] = 1 when side s owns at
+ * least one PUT.  fk != 0: keys are addressed by stride, koff is not read. */
+template <bool LDS_TAB>
+__global__ void __launch_bounds__(BLOCK)
+    k_split_classify(const uint8_t *keys, const uint64_t *koff, uint64_t fk, const uint64_t *sk,
+                     uint64_t n, uint64_t mask, uint64_t ppidx, uint64_t cpidx, uint8_t *side,
+                     uint64_t *wcnt, uint32_t *has_put)
+{
+    __shared__ uint64_t ltab[LDS_TAB ? 256 : 1];
+    if (LDS_TAB) {
+        for (uint32_t t = threadIdx.x; t < 256; t += blockDim.x)
+            ltab[t] = d_crc64_table[t];
+        __syncthreads();
+    }
+    const uint64_t lane = threadIdx.x & (WAVE - 1);
+    const uint64_t nw = (n + WAVE - 1) / WAVE;
+    const uint64_t n_waves = (gridDim.x * (uint64_t)blockDim.x) / WAVE;
+    bool put_p = false, put_c = false;
+    /* whole waves iterate together: the ballots need every lane present */
+    for (uint64_t w = (blockIdx.x * (uint64_t)blockDim.x + threadIdx.x) / WAVE; w < nw;
+         w += n_waves) {
+        uint64_t i = w * WAVE + lane;
+        uint32_t s = SPLIT_OOB;
+        bool put = false;
+        if (i < n) {
+            uint64_t ko = fk ? i * fk : koff[i];
+            uint64_t kl = fk ? fk : koff[i + 1] - ko;
+            const uint8_t *k = keys + ko;
+            s = SPLIT_PARENT; /* a key too short to carry a hashkey length */
+            if (kl >= 2) {
+                uint64_t hl = ((uint64_t)k[0] << 8) | k[1];
+                if (hl == 0 || hl > kl - 2)
+                    hl = kl - 2;
+                uint64_t t = split_crc64<LDS_TAB>(ltab, k + 2, hl) & mask;
+                s = t == ppidx ? SPLIT_PARENT : (t == cpidx ? SPLIT_CHILD : SPLIT_NONE);
+            }
+            side[i] = (uint8_t)s;
+            put = (sk[i] & 1) == 0;
+        }
+        unsigned long long bp = __ballot(s == SPLIT_PARENT);
+        unsigned long long bc = __ballot(s == SPLIT_CHILD);
+        if (lane == 0) {
+            wcnt[w] = (uint64_t)__popcll(bp);
+            wcnt[nw + w] = (uint64_t)__popcll(bc);
+        }
+        put_p |= put && s == SPLIT_PARENT;
+        put_c |= put && s == SPLIT_CHILD;
+    }
+    if (put_p)
+        has_put[SPLIT_PARENT] = 1u;
+    if (put_c)
+        has_put[SPLIT_CHILD] = 1u;
+}
+
+/* variable-length runs: per-record key / value bytes of side s (0 for the
+ * others), the input of the byte-offset scans.  A null output is skipped
+ * (that column is fixed-stride). */
+__global__ void k_split_sizes(const uint8_t *side, uint32_t s, const uint64_t *koff,
+                              const uint64_t *voff, uint64_t n, uint64_t *ksz, uint64_t *vsz)
+{
+    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n;
+         i += gridDim.x * (uint64_t)blockDim.x) {
+        bool mine = side[i] == s;
+        if (ksz)
+            ksz[i] = mine ? koff[i + 1] - koff[i] : 0;
+        if (vsz)
+            vsz[i] = mine ? voff[i + 1] - voff[i] : 0;
+    }
+}
+
+/* rank side s's records and write everything but the key/value bytes:
+ * osk, 0-based okoff/ovoff (n_side+1 entries) and the per-row source
+ * addresses the chunk copies read.  wbase = this side's section of the
+ * scanned wave counts, bias = what the scan accumulated before that section.
+ * fk / fv != 0: offsets are rank x stride; else kpos / vpos hold them. */
+__global__ void __launch_bounds__(BLOCK)
+    k_split_scatter(const uint8_t *keys, const uint64_t *koff, const uint8_t *vals,
+                    const uint64_t *voff, const uint64_t *sk, uint64_t n, uint64_t fk,
+                    uint64_t fv, const uint8_t *side, uint32_t s, const uint64_t *wbase,
+                    uint64_t bias, const uint64_t *kpos, const uint64_t *vpos, uint64_t n_side,
+                    uint64_t kbytes, uint64_t vbytes, uint64_t *okoff, uint64_t *ovoff,
+                    uint64_t *osk, uint64_t *row_ksrc, uint64_t *row_vsrc)
+{
+    const uint64_t lane = threadIdx.x & (WAVE - 1);
+    const uint64_t nw = (n + WAVE - 1) / WAVE;
+    const uint64_t n_waves = (gridDim.x * (uint64_t)blockDim.x) / WAVE;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        okoff[n_side] = kbytes;
+        ovoff[n_side] = vbytes;
+    }
+    for (uint64_t w = (blockIdx.x * (uint64_t)blockDim.x + threadIdx.x) / WAVE; w < nw;
+         w += n_waves) {
+        uint64_t i = w * WAVE + lane;
+        bool mine = i < n && side[i] == s;
+        unsigned long long b = __ballot(mine);
+        if (!mine)
+            continue;
+        uint64_t r = wbase[w] - bias + (uint64_t)__popcll(b & ((1ull << lane) - 1));
+        if (r >= n_side)
+            continue; /* cannot happen: counts and side[] come from one pass */
+        osk[r] = sk[i];
+        okoff[r] = fk ? r * fk : kpos[i];
+        ovoff[r] = fv ? r * fv : vpos[i];
+        row_ksrc[r] = (uint64_t)(keys + (fk ? i * fk : koff[i]));
+        row_vsrc[r] = (uint64_t)(vals + (fv ? i * fv : voff[i]));
+    }
+}
+
+void launch_split_classify(const uint8_t *keys, const uint64_t *koff, uint64_t fk,
+                           const uint64_t *sk, uint64_t n, uint64_t mask, uint64_t ppidx,
+                           uint64_t cpidx, uint8_t *d_side, uint64_t *d_wcnt, uint32_t *d_has_put,
+                           int lds_table, hipStream_t s)
+{
+    if (lds_table)
+        k_split_classify<true><<<grid_for(n, BLOCK), BLOCK, 0, s>>>(
+            keys, koff, fk, sk, n, mask, ppidx, cpidx, d_side, d_wcnt, d_has_put);
+    else
+        k_split_classify<false><<<grid_for(n, BLOCK), BLOCK, 0, s>>>(
+            keys, koff, fk, sk, n, mask, ppidx, cpidx, d_side, d_wcnt, d_has_put);
+}
+
+void launch_split_sizes(const uint8_t *d_side, uint32_t side, const uint64_t *koff,
+                        const uint64_t *voff, uint64_t n, uint64_t *d_ksz, uint64_t *d_vsz,
+                        hipStream_t s)
+{
+    k_split_sizes<<<grid_for(n, BLOCK), BLOCK, 0, s>>>(d_side, side, koff, voff, n, d_ksz, d_vsz);
+}
+
+void launch_split_scatter(const uint8_t *keys, const uint64_t *koff, const uint8_t *vals,
+                          const uint64_t *voff, const uint64_t *sk, uint64_t n, uint64_t fk,
+                          uint64_t fv, const uint8_t *d_side, uint32_t side,
+                          const uint64_t *d_wbase, uint64_t bias, const uint64_t *d_kpos,
+                          const uint64_t *d_vpos, uint64_t n_side, uint64_t kbytes,
+                          uint64_t vbytes, uint64_t *d_okoff, uint64_t *d_ovoff, uint64_t *d_osk,
+                          uint64_t *d_row_ksrc, uint64_t *d_row_vsrc, hipStream_t s)
+{
+    k_split_scatter<<<grid_for(n, BLOCK), BLOCK, 0, s>>>(
+        keys, koff, vals, voff, sk, n, fk, fv, d_side, side, d_wbase, bias, d_kpos, d_vpos,
+        n_side, kbytes, vbytes, d_okoff, d_ovoff, d_osk, d_row_ksrc, d_row_vsrc);
+}
+
+/* move one column's bytes (keys or values) of a split side: rows gathered
+ * from d_row_src into the packed d_out.  stride != 0: every row has that
+ * length; else d_row_off[n_rows+1] holds the 0-based output offsets and
+ * d_anchor (((bytes+15)>>10)+1 words) is scratch for the chunk->row search */
+void launch_split_copy(const uint64_t *d_row_src, const uint64_t *d_row_off, uint64_t n_rows,
+                       uint64_t stride, uint64_t bytes, uint64_t *d_anchor, uint8_t *d_out,
+                       hipStream_t s)
+{
+    if (bytes == 0 || n_rows == 0)
+        return;
+    if (stride && (stride & 15) == 0) {
+        k_copy_chunks_fixed<<<grid_for(bytes >> 4, BLOCK), BLOCK, 0, s>>>(d_row_src, n_rows,
+                                                                         stride, d_out);
+    } else if (stride) {
+        k_copy_rows_fixed<<<grid_for(n_rows, BLOCK), BLOCK, 0, s>>>(d_row_src, n_rows, stride,
+                                                                   d_out);
+    } else {
+        uint64_t anch = ((bytes + 15) >> 4 >> 6) + 1;
+        k_chunk_anchors<<<grid_for(anch, BLOCK), BLOCK, 0, s>>>(d_row_off, n_rows, anch,
+                                                               d_anchor);
+        k_copy_chunks<<<grid_for((bytes + 15) >> 4, BLOCK), BLOCK, 0, s>>>(
+            d_row_off, d_row_src, n_rows, bytes, d_anchor, anch, d_out);
+    }
 }
