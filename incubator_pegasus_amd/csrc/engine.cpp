@@ -608,6 +608,22 @@ struct RunBuf {
     uint32_t fixed_vlen = 0;   /* constant encoded-value stride (0=variable) */
     uint32_t fixed_vlen_put = 0; /* constant PUT-value stride (emit output) */
 };
+/* what a run's allocation does on a full device (HipEngine::col_alloc) */
+enum class RunAlloc { Abort, Try, Arena };
+/* first and last key of a run, cut to the 32 bytes lcp_exact32 looks at */
+struct KeyEnds {
+    uint8_t a[32], b[32];
+    uint64_t al = 0, bl = 0;
+};
+/* the stride field `f` when every run of the window shares it, else 0:
+ * outputs are verbatim-length copies of inputs, so a shared stride survives */
+static uint32_t shared_stride(const RunBuf *wr, int R, uint32_t RunBuf::*f)
+{
+    for (int r = 1; r < R; r++)
+        if (wr[r].*f != wr[0].*f)
+            return 0;
+    return R ? wr[0].*f : 0;
+}
 
 struct HipScanCtx {
     int64_t id = 0;
@@ -984,74 +1000,199 @@ struct HipEngine {
         r = RunBuf();
     }
 
-    /* the three run-column builders below abort on a full device, like every
-     * HIP_OK; with try_alloc they return false instead (the split unwinds) */
-    bool col_alloc(uint64_t **p, uint64_t bytes, bool try_alloc)
+    /* ---- run creation: every new run goes through alloc_base (or
+     * upload_run, which wraps it), then finish_run, then the run list with
+     * runs_changed(); whoever frees a run calls before_run_free() first ---- */
+
+    /* one device buffer of a run.  Abort: a full device ends the process,
+     * like every HIP_OK.  Try: false, with the sticky HIP error cleared.
+     * Arena: scratch memory, for a run that is dropped with the operation. */
+    template <typename T> bool col_alloc(T **p, uint64_t bytes, RunAlloc mode)
     {
-        if (!try_alloc) {
-            HIP_OK(hipMalloc(p, bytes));
+        if (mode == RunAlloc::Arena) {
+            *p = talloc<T>(bytes);
             return true;
         }
-        return hipMalloc(p, bytes) == hipSuccess;
+        hipError_t rc = hipMalloc(p, bytes ? bytes : 1);
+        if (mode == RunAlloc::Abort)
+            HIP_OK(rc);
+        if (rc != hipSuccess)
+            (void)hipGetLastError();
+        return rc == hipSuccess;
     }
+    /* the five base columns of an n-record run; false (Try only) leaves
+     * nothing allocated */
+    bool alloc_base(RunBuf &r, uint64_t n, uint64_t kbytes, uint64_t vbytes, RunAlloc mode)
+    {
+        r.n = n;
+        if (col_alloc(&r.keys, kbytes, mode) && col_alloc(&r.koff, (n + 1) * 8, mode) &&
+            col_alloc(&r.vals, vbytes, mode) && col_alloc(&r.voff, (n + 1) * 8, mode) &&
+            col_alloc(&r.sk, n * 8, mode))
+            return true;
+        free_run(r);
+        return false;
+    }
+    /* a validated sorted run arriving from the host: base columns, strides,
+     * and its first/last key in *ends for finish_run.  false (Try only) = the
+     * device is full and nothing is left allocated. */
+    bool upload_run(RunBuf &r, const uint8_t *keys, const uint64_t *koff, const uint8_t *vals,
+                    const uint64_t *voff, const uint64_t *sk, uint64_t n, RunAlloc mode,
+                    KeyEnds *ends)
+    {
+        if (!alloc_base(r, n, koff[n], voff[n], mode))
+            return false;
+        const struct {
+            void *dst;
+            const void *src;
+            uint64_t bytes;
+        } cols[5] = {{r.keys, keys, koff[n]},
+                     {r.koff, koff, (n + 1) * 8},
+                     {r.vals, vals, voff[n]},
+                     {r.voff, voff, (n + 1) * 8},
+                     {r.sk, sk, n * 8}};
+        for (auto &c : cols) {
+            if (!c.bytes)
+                continue;
+            hipError_t rc = hipMemcpy(c.dst, c.src, c.bytes, hipMemcpyHostToDevice);
+            if (mode == RunAlloc::Abort)
+                HIP_OK(rc);
+            if (rc != hipSuccess) {
+                (void)hipGetLastError();
+                free_run(r);
+                return false;
+            }
+        }
+        r.fixed_klen = detect_fixed_klen(koff, n);
+        r.fixed_vlen = detect_fixed_vlen(voff, n);
+        r.fixed_vlen_put = detect_fixed_vlen_put(voff, sk, n);
+        *ends = KeyEnds();
+        if (n) {
+            ends->al = std::min<uint64_t>(koff[1] - koff[0], 32);
+            ends->bl = std::min<uint64_t>(koff[n] - koff[n - 1], 32);
+            memcpy(ends->a, keys + koff[0], ends->al);
+            memcpy(ends->b, keys + koff[n - 1], ends->bl);
+        }
+        return true;
+    }
+    /* first/last key of a run built on the device (n > 0, fixed_klen set by
+     * the caller).  A fixed stride gives both addresses without the offsets. */
+    KeyEnds read_key_ends(const RunBuf &r)
+    {
+        KeyEnds k;
+        const uint64_t fk = r.fixed_klen;
+        uint64_t fo[2] = {0, fk}, lo[2] = {(r.n - 1) * fk, r.n * fk};
+        if (!fk) {
+            HIP_OK(hipMemcpy(fo, r.koff, 16, hipMemcpyDeviceToHost));
+            HIP_OK(hipMemcpy(lo, r.koff + (r.n - 1), 16, hipMemcpyDeviceToHost));
+        }
+        k.al = std::min<uint64_t>(fo[1] - fo[0], 32);
+        k.bl = std::min<uint64_t>(lo[1] - lo[0], 32);
+        HIP_OK(hipMemcpy(k.a, r.keys + fo[0], k.al ? k.al : 1, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(k.b, r.keys + lo[0], k.bl ? k.bl : 1, hipMemcpyDeviceToHost));
+        return k;
+    }
+
+    /* the three column builders only enqueue on `stream`; finish_run drains.
+     * false = a Try allocation failed (what was allocated stays in r). */
     /* packed 8B-strided probe words for the single-word search mode */
-    bool build_tails(RunBuf &r, bool try_alloc = false)
+    bool build_tails(RunBuf &r, RunAlloc mode)
     {
         if (r.n == 0 || r.fixed_klen < 8 || r.lcp_exact + 8 < r.fixed_klen)
             return true;
-        if (!col_alloc(&r.tails, r.n * 8, try_alloc))
+        if (!col_alloc(&r.tails, r.n * 8, mode))
             return false;
         launch_build_tails(r.keys, r.fixed_klen, r.n, r.tails, stream);
-        HIP_OK(hipStreamSynchronize(stream));
         return true;
     }
 
     /* disposition column (expire<<32|kind): one 8B gather replaces the
      * sk + voff + value-header chain in filter/scan-state evaluation */
-    bool build_meta(RunBuf &r, bool try_alloc = false)
+    bool build_meta(RunBuf &r, RunAlloc mode)
     {
         if (r.n == 0)
             return true;
-        if (!col_alloc(&r.meta, r.n * 8, try_alloc))
+        if (!col_alloc(&r.meta, r.n * 8, mode))
             return false;
         launch_build_meta(r.vals, r.voff, r.fixed_vlen, r.sk, r.n, data_version, r.meta,
                           stream);
-        HIP_OK(hipStreamSynchronize(stream));
         return true;
     }
 
     /* §8(f)3: ~10 bits/key blocked bloom, built once per run on device */
-    /* want: -1 = this handle's rocksdb.filter_type, else 0/1 (the split
-     * builds the child's runs and applies the child's setting) */
-    bool build_bloom(RunBuf &r, bool try_alloc = false, int want = -1)
+    bool build_bloom(RunBuf &r, RunAlloc mode)
     {
-        if (!(want < 0 ? bloom_enabled : want != 0) || r.n == 0)
+        if (r.n == 0)
             return true;
         uint64_t n_blocks = (r.n * 10 + 511) / 512;
         if (n_blocks == 0)
             n_blocks = 1;
-        if (!col_alloc(&r.bloom, n_blocks * 64, try_alloc) ||
-            !col_alloc(&r.pfx_bloom, n_blocks * 64, try_alloc))
+        if (!col_alloc(&r.bloom, n_blocks * 64, mode) ||
+            !col_alloc(&r.pfx_bloom, n_blocks * 64, mode))
             return false;
+        DevRun dr = to_dev(r);
         HIP_OK(hipMemsetAsync(r.bloom, 0, n_blocks * 64, stream));
-        DevRun dr{};
-        dr.keys = r.keys;
-        dr.koff = r.koff;
-        dr.vals = r.vals;
-        dr.voff = r.voff;
-        dr.sk = r.sk;
-        dr.n = r.n;
         launch_bloom_build(dr, r.bloom, n_blocks, stream);
         /* §8(f)3 second half: hashkey-prefix bloom (the reference's
          * prefix-extractor filter, _init.cpp:816-841, hashkey_transform.h) */
         HIP_OK(hipMemsetAsync(r.pfx_bloom, 0, n_blocks * 64, stream));
         launch_bloom_pfx_build(dr, r.pfx_bloom, n_blocks, stream);
-        HIP_OK(hipStreamSynchronize(stream));
         r.bloom_blocks = n_blocks;
         r.pfx_bloom_blocks = n_blocks;
         return true;
     }
 
+    /* the derived half of run creation: shared-prefix fields from the run's
+     * first/last key (`host_ends` from upload_run; null = the run was built
+     * on the device, read them back), then the tails, meta and bloom
+     * columns, one stream drain for all three.  `bloom` is the owning
+     * handle's rocksdb.filter_type (the split passes the child's for the
+     * child's runs).  false = a Try allocation failed; the stream is drained
+     * first, because the caller frees buffers that enqueued builds may still
+     * read. */
+    bool finish_run(RunBuf &r, const KeyEnds *host_ends, RunAlloc mode, bool bloom)
+    {
+        const KeyEnds ends = host_ends ? *host_ends : read_key_ends(r);
+        set_pfx(lcp_exact32(ends.a, ends.al, ends.b, ends.bl), &r.pfx_skip, &r.lcp_exact);
+        bool ok = build_tails(r, mode) && build_meta(r, mode) && (!bloom || build_bloom(r, mode));
+        HIP_OK(hipStreamSynchronize(stream));
+        return ok;
+    }
+
+    /* the run list (or a column of one of its runs) changed */
+    void runs_changed()
+    {
+        d_runs_dirty = true;
+        ldst_elig_cache = -1;
+    }
+    /* must precede freeing any run: the resident serving kernel and every
+     * parked scan view still reference it.  Appending a run needs neither. */
+    void before_run_free()
+    {
+        server_quit_sync();
+        invalidate_ctxs();
+    }
+
+    static DevRun to_dev(const RunBuf &r)
+    {
+        DevRun d{};
+        d.keys = r.keys;
+        d.koff = r.koff;
+        d.vals = r.vals;
+        d.voff = r.voff;
+        d.sk = r.sk;
+        d.n = r.n;
+        d.bloom = r.bloom;
+        d.bloom_blocks = r.bloom_blocks;
+        d.fixed_klen = r.fixed_klen;
+        d.pfx_skip = r.pfx_skip;
+        d.lcp_exact = r.lcp_exact;
+        d.tails = r.tails;
+        d.pfx_bloom = r.pfx_bloom;
+        d.pfx_bloom_blocks = r.pfx_bloom_blocks;
+        d.meta = r.meta;
+        d.fixed_vlen = r.fixed_vlen;
+        return d;
+    }
     DevRun *dev_runs()
     {
         if (d_runs_dirty) {
@@ -1059,26 +1200,8 @@ struct HipEngine {
             if (d_runs)
                 (void)hipFree(d_runs);
             std::vector<DevRun> h(runs.size() ? runs.size() : 1);
-            for (size_t i = 0; i < runs.size(); i++) {
-                DevRun d{};
-                d.keys = runs[i].keys;
-                d.koff = runs[i].koff;
-                d.vals = runs[i].vals;
-                d.voff = runs[i].voff;
-                d.sk = runs[i].sk;
-                d.n = runs[i].n;
-                d.bloom = runs[i].bloom;
-                d.bloom_blocks = runs[i].bloom_blocks;
-                d.fixed_klen = runs[i].fixed_klen;
-                d.pfx_skip = runs[i].pfx_skip;
-                d.lcp_exact = runs[i].lcp_exact;
-                d.tails = runs[i].tails;
-                d.pfx_bloom = runs[i].pfx_bloom;
-                d.pfx_bloom_blocks = runs[i].pfx_bloom_blocks;
-                d.meta = runs[i].meta;
-                d.fixed_vlen = runs[i].fixed_vlen;
-                h[i] = d;
-            }
+            for (size_t i = 0; i < runs.size(); i++)
+                h[i] = to_dev(runs[i]);
             HIP_OK(hipMalloc(&d_runs, h.size() * sizeof(DevRun)));
             HIP_OK(hipMemcpy(d_runs, h.data(), h.size() * sizeof(DevRun), hipMemcpyHostToDevice));
             d_runs_dirty = false;
@@ -1137,21 +1260,6 @@ struct HipEngine {
         HIP_OK(hipMalloc(&d, n ? n : 1));
         if (n)
             HIP_OK(hipMemcpy(d, p, n, hipMemcpyHostToDevice));
-        return d;
-    }
-
-    /* ingest-path variant: a full device returns null (the caller unwinds
-     * and reports kIOError, like rocksdb's background write errors) instead
-     * of aborting the process */
-    uint8_t *upload_bytes_try(const void *p, uint64_t n)
-    {
-        uint8_t *d = nullptr;
-        if (hipMalloc(&d, n ? n : 1) != hipSuccess)
-            return nullptr;
-        if (n && hipMemcpy(d, p, n, hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(d);
-            return nullptr;
-        }
         return d;
     }
 
@@ -1438,35 +1546,18 @@ static int32_t engine_flush(HipEngine *e); /* write path, defined below */
 
 /* internal: upload a prepared sorted run (validation already established);
  * kIOError (with the partial run unwound) when the device is full */
-static int32_t ingest_prepared(HipEngine *e, const std::string &keys,
-                               const std::vector<uint64_t> &koff, const std::string &vals,
-                               const std::vector<uint64_t> &voff,
-                               const std::vector<uint64_t> &sk)
+static int32_t ingest_prepared(HipEngine *e, const uint8_t *keys, const uint64_t *koff,
+                               const uint8_t *vals, const uint64_t *voff, const uint64_t *sk,
+                               uint64_t n)
 {
     RunBuf r;
-    r.n = sk.size();
-    r.keys = e->upload_bytes_try(keys.data(), keys.size());
-    r.koff = (uint64_t *)e->upload_bytes_try(koff.data(), koff.size() * 8);
-    r.vals = e->upload_bytes_try(vals.data(), vals.size());
-    r.voff = (uint64_t *)e->upload_bytes_try(voff.data(), voff.size() * 8);
-    r.sk = (uint64_t *)e->upload_bytes_try(sk.data(), sk.size() * 8);
-    if (!r.keys || !r.koff || !r.vals || !r.voff || !r.sk) {
-        e->free_run(r);
+    KeyEnds ends;
+    if (!e->upload_run(r, keys, koff, vals, voff, sk, n, RunAlloc::Try, &ends))
         return RRDB_IO_ERROR;
-    }
-    r.fixed_klen = detect_fixed_klen(koff.data(), r.n);
-    r.fixed_vlen = detect_fixed_vlen(voff.data(), r.n);
-    r.fixed_vlen_put = detect_fixed_vlen_put(voff.data(), sk.data(), r.n);
-    set_pfx(lcp_exact32((const uint8_t *)keys.data(), koff[1] - koff[0],
-                        (const uint8_t *)keys.data() + koff[r.n - 1],
-                        koff[r.n] - koff[r.n - 1]),
-            &r.pfx_skip, &r.lcp_exact);
-    e->build_tails(r);
-    e->build_meta(r);
-    e->build_bloom(r);
+    /* the derived columns abort on a full device, as they always have here */
+    e->finish_run(r, &ends, RunAlloc::Abort, e->bloom_enabled);
     e->runs.push_back(r);
-    e->d_runs_dirty = true;
-    e->ldst_elig_cache = -1;
+    e->runs_changed();
     return RRDB_OK;
 }
 
@@ -1611,9 +1702,10 @@ int32_t rrdb_set_envs(void *h, const char *const *keys, const char *const *value
                         (void)hipFree(r.meta);
                         r.meta = nullptr;
                     }
-                    e->build_meta(r);
+                    e->build_meta(r, RunAlloc::Abort);
                 }
-                e->d_runs_dirty = true;
+                HIP_OK(hipStreamSynchronize(e->stream));
+                e->runs_changed();
             }
         } else if (k == "replica.rocksdb_iteration_threshold_time_ms") {
             e->iter_time_ms = (uint64_t)atoll(v.c_str());
@@ -1697,33 +1789,13 @@ int32_t rrdb_ingest_run(void *h, const uint8_t *keys, const uint64_t *key_offs,
         }
     }
     e->activate();
-    RunBuf r;
-    r.n = n;
-    r.keys = e->upload_bytes_try(keys, key_offs[n]);
-    r.koff = (uint64_t *)e->upload_bytes_try(key_offs, (n + 1) * 8);
-    r.vals = e->upload_bytes_try(values, val_offs[n]);
-    r.voff = (uint64_t *)e->upload_bytes_try(val_offs, (n + 1) * 8);
-    r.sk = (uint64_t *)e->upload_bytes_try(seq_kind, n * 8);
-    if (!r.keys || !r.koff || !r.vals || !r.voff || !r.sk) {
-        e->free_run(r);
-        return RRDB_IO_ERROR;
-    }
-    r.fixed_klen = detect_fixed_klen(key_offs, n);
-    r.fixed_vlen = detect_fixed_vlen(val_offs, n);
-    r.fixed_vlen_put = detect_fixed_vlen_put(val_offs, seq_kind, n);
-    set_pfx(lcp_exact32(keys + key_offs[0], key_offs[1] - key_offs[0],
-                        keys + key_offs[n - 1], key_offs[n] - key_offs[n - 1]),
-            &r.pfx_skip, &r.lcp_exact);
+    int32_t rc = ingest_prepared(e, keys, key_offs, values, val_offs, seq_kind, n);
+    if (rc != RRDB_OK)
+        return rc;
     uint64_t mx = 0;
     for (uint64_t i = 0; i < n; i++)
         mx = std::max(mx, seq_kind[i] >> 1);
     e->next_seq_floor = mx + 1;
-    e->build_tails(r);
-    e->build_meta(r);
-    e->build_bloom(r);
-    e->runs.push_back(r);
-    e->d_runs_dirty = true;
-    e->ldst_elig_cache = -1;
     return RRDB_OK;
 }
 
@@ -3061,14 +3133,8 @@ static int32_t compact_begin(HipEngine *e, const rrdb_compact_options *opts, uin
      * stride (the hashkey-table schema), so output offsets derive from the
      * keep count — the ksz/vsz arrays and two of the three full-length
      * prefix sums are skipped entirely */
-    uint64_t ffk = R == 0 ? 0 : wr[0].fixed_klen;
-    uint64_t ffv = R == 0 ? 0 : wr[0].fixed_vlen_put;
-    for (int r = 0; r < R; r++) {
-        if (wr[r].fixed_klen != ffk)
-            ffk = 0;
-        if (wr[r].fixed_vlen_put != ffv)
-            ffv = 0;
-    }
+    uint64_t ffk = shared_stride(wr, R, &RunBuf::fixed_klen);
+    uint64_t ffv = shared_stride(wr, R, &RunBuf::fixed_vlen_put);
     /* a non-bottommost output can hold tombstones (kept or converted), whose
      * rows are not fv long: it always takes the per-row-size path */
     bool fixed_emit = ffk > 0 && ffv > 0 && emit_mode == 2 && bottommost;
@@ -3253,25 +3319,10 @@ static int32_t compact_finish(HipEngine *e, rrdb_compact_stats *stats)
     RunBuf nr;
     bool keep_inputs = e->pend.keep_inputs;
     if (n_out > 0) {
-        nr.n = n_out;
-        /* output keys are verbatim copies of input keys, so a stride shared
-         * by every input run is preserved */
-        nr.fixed_klen = R == 0 ? 0 : wr[0].fixed_klen;
-        for (int r = 0; r < R; r++)
-            if (wr[r].fixed_klen != nr.fixed_klen)
-                nr.fixed_klen = 0;
-        /* output values are verbatim-length copies of input values, so a
-         * stride shared by every input run is preserved too */
-        nr.fixed_vlen = R == 0 ? 0 : wr[0].fixed_vlen;
-        for (int r = 0; r < R; r++)
-            if (wr[r].fixed_vlen != nr.fixed_vlen)
-                nr.fixed_vlen = 0;
-        /* the output's PUTs are verbatim-length copies of input PUTs: the
-         * shared put-stride of the inputs (when one exists) is preserved */
-        nr.fixed_vlen_put = R == 0 ? 0 : wr[0].fixed_vlen_put;
-        for (int r = 0; r < R; r++)
-            if (wr[r].fixed_vlen_put != nr.fixed_vlen_put)
-                nr.fixed_vlen_put = 0;
+        /* keys, values and PUT values come out as verbatim-length copies */
+        nr.fixed_klen = shared_stride(wr, R, &RunBuf::fixed_klen);
+        nr.fixed_vlen = shared_stride(wr, R, &RunBuf::fixed_vlen);
+        nr.fixed_vlen_put = shared_stride(wr, R, &RunBuf::fixed_vlen_put);
         if (e->pend.bottommost) {
             /* the merged output holds only PUTs: its plain stride equals
              * the put-stride */
@@ -3284,20 +3335,8 @@ static int32_t compact_finish(HipEngine *e, rrdb_compact_stats *stats)
         } else if (!nr.fixed_vlen) {
             nr.fixed_vlen = nr.fixed_vlen_put; /* only PUTs came out */
         }
-        if (keep_inputs) {
-            /* output is dropped at the end of the pass: pooled temporaries */
-            nr.keys = e->talloc<uint8_t>(kbytes);
-            nr.vals = e->talloc<uint8_t>(vbytes);
-            nr.koff = e->talloc<uint64_t>((n_out + 1) * 8);
-            nr.voff = e->talloc<uint64_t>((n_out + 1) * 8);
-            nr.sk = e->talloc<uint64_t>(n_out * 8);
-        } else {
-            HIP_OK(hipMalloc(&nr.keys, kbytes ? kbytes : 1));
-            HIP_OK(hipMalloc(&nr.vals, vbytes ? vbytes : 1));
-            HIP_OK(hipMalloc(&nr.koff, (n_out + 1) * 8));
-            HIP_OK(hipMalloc(&nr.voff, (n_out + 1) * 8));
-            HIP_OK(hipMalloc(&nr.sk, n_out * 8));
-        }
+        /* keep_inputs drops the output at the end of the pass: arena memory */
+        e->alloc_base(nr, n_out, kbytes, vbytes, keep_inputs ? RunAlloc::Arena : RunAlloc::Abort);
         HIP_OK(hipEventRecord(ev[3], e->stream));
         if (e->emit_mode == 2 || e->pend.chunked || e->pend.fk || e->pend.no_rewrite) {
             uint64_t *d_row_ksrc = e->talloc<uint64_t>(n_out * 8);
@@ -3340,30 +3379,17 @@ static int32_t compact_finish(HipEngine *e, rrdb_compact_stats *stats)
     if (keep_inputs) {
         /* benchmarking: the pass ran in full; drop the output, keep inputs */
     } else {
-        e->server_quit_sync(); /* the resident kernel holds the freed runs */
-        e->invalidate_ctxs(); /* parked views reference the freed runs */
+        e->before_run_free();
         /* only the window's runs go; the merged run takes their place at
          * index `first`, older and newer runs stay where they are */
         for (int r = 0; r < R; r++)
             e->free_run(e->runs[first + r]);
         e->runs.erase(e->runs.begin() + first, e->runs.begin() + first + R);
         if (n_out > 0) {
-            uint64_t fo2[2], lo2[2];
-            uint8_t h32[32], t32[32];
-            HIP_OK(hipMemcpy(fo2, nr.koff, 16, hipMemcpyDeviceToHost));
-            HIP_OK(hipMemcpy(lo2, nr.koff + (n_out - 1), 16, hipMemcpyDeviceToHost));
-            uint64_t fl = std::min<uint64_t>(fo2[1] - fo2[0], 32);
-            uint64_t ll = std::min<uint64_t>(lo2[1] - lo2[0], 32);
-            HIP_OK(hipMemcpy(h32, nr.keys + fo2[0], fl ? fl : 1, hipMemcpyDeviceToHost));
-            HIP_OK(hipMemcpy(t32, nr.keys + lo2[0], ll ? ll : 1, hipMemcpyDeviceToHost));
-            set_pfx(lcp_exact32(h32, fl, t32, ll), &nr.pfx_skip, &nr.lcp_exact);
-            e->build_tails(nr);
-            e->build_meta(nr);
-            e->build_bloom(nr);
+            e->finish_run(nr, nullptr, RunAlloc::Abort, e->bloom_enabled);
             e->runs.insert(e->runs.begin() + first, nr);
         }
-        e->d_runs_dirty = true;
-        e->ldst_elig_cache = -1;
+        e->runs_changed();
     }
     if (stats)
         *stats = st;
@@ -3493,26 +3519,10 @@ struct SplitTmp {
     double emit_ms = 0.0;
 };
 
-/* first/last key -> set_pfx, then the tails / meta / bloom columns, as every
- * run-creation path does.  false = the device is full (caller frees r). */
-static bool split_finish_run(HipEngine *e, RunBuf &r, bool bloom)
-{
-    uint64_t fo2[2], lo2[2];
-    uint8_t h32[32], t32[32];
-    HIP_OK(hipMemcpy(fo2, r.koff, 16, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(lo2, r.koff + (r.n - 1), 16, hipMemcpyDeviceToHost));
-    uint64_t fl = std::min<uint64_t>(fo2[1] - fo2[0], 32);
-    uint64_t ll = std::min<uint64_t>(lo2[1] - lo2[0], 32);
-    HIP_OK(hipMemcpy(h32, r.keys + fo2[0], fl ? fl : 1, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(t32, r.keys + lo2[0], ll ? ll : 1, hipMemcpyDeviceToHost));
-    set_pfx(lcp_exact32(h32, fl, t32, ll), &r.pfx_skip, &r.lcp_exact);
-    return e->build_tails(r, true) && e->build_meta(r, true) &&
-           e->build_bloom(r, true, bloom ? 1 : 0);
-}
-
 /* Build side s (0 parent, 1 child) of `src` as a finished run in *out and
- * its key+value bytes in *bytes.  si.cnt[s] > 0.  false = an allocation
- * failed; nothing is left allocated and src is untouched. */
+ * its key+value bytes in *bytes.  si.cnt[s] > 0.  `bloom` is the
+ * rocksdb.filter_type of the handle that will own the run.  false = an
+ * allocation failed; nothing is left allocated and src is untouched. */
 static bool split_emit_side(HipEngine *e, const RunBuf &src, const SplitRunInfo &si, int s,
                             SplitTmp &t, bool bloom, RunBuf *out, uint64_t *bytes)
 {
@@ -3541,16 +3551,8 @@ static bool split_emit_side(HipEngine *e, const RunBuf &src, const SplitRunInfo 
             vbytes = tot[2] + tot[3];
     }
     RunBuf r;
-    r.n = ns;
-    if (hipMalloc(&r.keys, kbytes ? kbytes : 1) != hipSuccess ||
-        hipMalloc(&r.vals, vbytes ? vbytes : 1) != hipSuccess ||
-        hipMalloc(&r.koff, (ns + 1) * 8) != hipSuccess ||
-        hipMalloc(&r.voff, (ns + 1) * 8) != hipSuccess ||
-        hipMalloc(&r.sk, ns * 8) != hipSuccess) {
-        (void)hipGetLastError();
-        e->free_run(r);
+    if (!e->alloc_base(r, ns, kbytes, vbytes, RunAlloc::Try))
         return false;
-    }
     HIP_OK(hipEventRecord(t.ev[0], e->stream));
     launch_split_scatter(src.keys, src.koff, src.vals, src.voff, src.sk, n, fk, fv, si.side,
                          (uint32_t)s, si.wbase + (s ? si.nw : 0), s ? si.cnt[0] : 0, t.kpos,
@@ -3569,8 +3571,7 @@ static bool split_emit_side(HipEngine *e, const RunBuf &src, const SplitRunInfo 
     r.fixed_klen = src.fixed_klen;
     r.fixed_vlen = src.fixed_vlen;
     r.fixed_vlen_put = si.has_put[s] ? src.fixed_vlen_put : 0;
-    if (!split_finish_run(e, r, bloom)) {
-        (void)hipGetLastError();
+    if (!e->finish_run(r, nullptr, RunAlloc::Try, bloom)) {
         e->free_run(r);
         return false;
     }
@@ -3714,8 +3715,7 @@ int32_t rrdb_split(void *parent, void *child, int32_t new_partition_count,
 
     /* phase B: prune the parent run by run.  From here the parent's run list
      * changes: retire its resident kernel and parked views first. */
-    p->server_quit_sync();
-    p->invalidate_ctxs();
+    p->before_run_free();
     std::vector<RunBuf> parent_runs;
     bool full = false;
     for (size_t i = 0; i < R; i++) {
@@ -3762,8 +3762,8 @@ int32_t rrdb_split(void *parent, void *child, int32_t new_partition_count,
     p->partition_version = c->partition_version = (int32_t)(npc - 1);
     /* later writes to the child outrank everything it inherited */
     c->next_seq_floor = p->next_seq_floor;
-    p->d_runs_dirty = c->d_runs_dirty = true;
-    p->ldst_elig_cache = c->ldst_elig_cache = -1;
+    p->runs_changed();
+    c->runs_changed();
     if (stats)
         *stats = st;
     return RRDB_OK;
@@ -3834,7 +3834,8 @@ static int32_t engine_flush(HipEngine *e)
         voff.push_back(vals.size());
         sk.push_back((std::get<1>(kv.second) << 1) | (uint64_t)std::get<2>(kv.second));
     }
-    int32_t rc = ingest_prepared(e, keys, koff, vals, voff, sk);
+    int32_t rc = ingest_prepared(e, (const uint8_t *)keys.data(), koff.data(),
+                                 (const uint8_t *)vals.data(), voff.data(), sk.data(), sk.size());
     if (rc != RRDB_OK)
         return rc; /* memtable retained: the write is not lost */
     e->memtable.clear();
@@ -4019,30 +4020,15 @@ int32_t rrdb_restore(void *h, const char *dir, uint64_t decree)
                 return RRDB_CORRUPTION; /* keys must be strictly increasing */
         }
         RunBuf r;
-        r.n = nrec;
-        r.keys = e->upload_bytes(keys.data(), keys.size());
-        r.koff = (uint64_t *)e->upload_bytes(koff.data(), koff.size());
-        r.vals = e->upload_bytes(vals.data(), vals.size());
-        r.voff = (uint64_t *)e->upload_bytes(voff.data(), voff.size());
-        r.sk = (uint64_t *)e->upload_bytes(sk.data(), sk.size());
-        r.fixed_klen = detect_fixed_klen((const uint64_t *)koff.data(), r.n);
-        r.fixed_vlen = detect_fixed_vlen((const uint64_t *)voff.data(), r.n);
-        r.fixed_vlen_put = detect_fixed_vlen_put((const uint64_t *)voff.data(),
-                                                 (const uint64_t *)sk.data(), r.n);
-        if (r.n) {
-            const uint64_t *ko = (const uint64_t *)koff.data();
-            set_pfx(lcp_exact32(keys.data() + ko[0], ko[1] - ko[0],
-                                keys.data() + ko[r.n - 1], ko[r.n] - ko[r.n - 1]),
-                    &r.pfx_skip, &r.lcp_exact);
-        }
-        e->build_tails(r); /* rebuilt, not serialized (like blooms) */
-        e->build_meta(r);
-        e->build_bloom(r);
+        KeyEnds ends;
+        e->upload_run(r, keys.data(), ko, vals.data(), vo, (const uint64_t *)sk.data(), nrec,
+                      RunAlloc::Abort, &ends);
+        /* derived columns are rebuilt, not serialized */
+        e->finish_run(r, &ends, RunAlloc::Abort, e->bloom_enabled);
         e->runs.push_back(r);
     }
     e->next_seq_floor = floor_;
-    e->d_runs_dirty = true;
-    e->ldst_elig_cache = -1;
+    e->runs_changed();
     return RRDB_OK;
 }
 
