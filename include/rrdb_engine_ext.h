@@ -71,6 +71,34 @@
  *     contexts are reclaimed as after a compaction (scan_next: kNotFound).
  *   - rrdb_phase_ms(parent, ...) reports split_classify, split_emit and
  *     split_total.
+ *
+ * Batched writes.  rrdb_put / rrdb_remove insert one record at a time into a
+ * host memtable; the reference applies a whole batch of mutations per decree
+ * (on_batched_write_requests, multi_put, multi_remove).  rrdb_write_batch
+ * takes such a batch unsorted, in commit order, duplicate keys allowed, and
+ * sorts and dedups it on the device.  The result is exactly what this
+ * sequence leaves behind, ending in one new run: flush the memtable; for
+ * i = 0..n-1 rrdb_put / rrdb_remove op i; rrdb_flush.
+ *   - Keys are full keys [u16 BE hklen][hashkey][sortkey], as rrdb_get takes
+ *     them.  Op i gets seqno next_seq_floor + i; on success the floor advances
+ *     by n_ops, superseded ops included.  Of several ops on one key the last
+ *     one wins and is the only one stored.
+ *   - A PUT value is encoded as rrdb_put encodes it: the header of the
+ *     handle's pegasus.data_version with timetag 0, and expire_ts == 0 with a
+ *     default_ttl env becomes epoch_now + default_ttl.  A remove is a
+ *     tombstone with an empty value.
+ *   - Pending memtable entries are older than the batch: they are flushed
+ *     first into a run of their own, and a failure of that flush is returned.
+ *   - Everything is validated before anything changes.  kInvalidArgument with
+ *     the handle as before: offsets that do not start at 0 or decrease; a key
+ *     shorter than 2 bytes; hklen > klen - 2 or hklen == 0xFFFF; a kind other
+ *     than 0/1; n_ops > 2^31 - 1; a split compaction or a pipelined count
+ *     scan pending.  n_ops == 0 is kOk and does nothing.
+ *   - Every allocation proportional to the batch may fail cleanly: on a full
+ *     device the call returns kIOError, no run is added, the floor is
+ *     unchanged, and a memtable flush that already happened stays.
+ *   - rrdb_phase_ms reports wb_sort, wb_emit and wb_total (device time), and
+ *     wb_stage and wb_upload (host time of the staging and of the copies).
  */
 #ifndef RRDB_ENGINE_EXT_H
 #define RRDB_ENGINE_EXT_H
@@ -132,6 +160,26 @@ typedef struct {
  * runs on the parent's stream. */
 int32_t rrdb_split(void *parent, void *child, int32_t new_partition_count,
                    rrdb_split_stats *stats);
+
+typedef struct {
+    uint64_t input_ops;       /* n_ops                                         */
+    uint64_t output_records;  /* records in the new run (one per distinct key) */
+    uint64_t superseded;      /* input_ops - output_records                    */
+    uint64_t puts, removes;   /* among the output records                      */
+    uint64_t key_bytes, value_bytes; /* of the new run (values encoded)        */
+} rrdb_write_batch_stats;
+
+/* Apply n_ops puts/removes, given unsorted in commit order with duplicate
+ * keys allowed, as one new run built on the device; see the header comment.
+ * keys / key_offs: full rocksdb keys, packed, n+1 offsets.  values /
+ * val_offs: user data, packed, n+1 offsets (a remove's span is ignored).
+ * expire_ts[n] is ignored for removes and may be null (all zero).  kinds[n]:
+ * RRDB_KIND_PUT / RRDB_KIND_DELETE. */
+int32_t rrdb_write_batch(void *h, uint64_t n_ops,
+                         const uint8_t *keys, const uint64_t *key_offs,
+                         const uint8_t *values, const uint64_t *val_offs,
+                         const uint32_t *expire_ts, const uint8_t *kinds,
+                         uint32_t epoch_now, rrdb_write_batch_stats *stats);
 
 #ifdef __cplusplus
 }

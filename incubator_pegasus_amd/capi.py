@@ -132,6 +132,18 @@ class _SplitStats(C.Structure):
     ]
 
 
+class _WriteBatchStats(C.Structure):
+    _fields_ = [
+        ("input_ops", C.c_uint64),
+        ("output_records", C.c_uint64),
+        ("superseded", C.c_uint64),
+        ("puts", C.c_uint64),
+        ("removes", C.c_uint64),
+        ("key_bytes", C.c_uint64),
+        ("value_bytes", C.c_uint64),
+    ]
+
+
 def _cslice(b: bytes, keep: list) -> _CSlice:
     """Build a _CSlice over a copy of b; the backing buffer is appended to
     `keep`, which the caller must hold alive across the C call (struct field
@@ -183,6 +195,17 @@ class SplitStats:
     parent_runs: int = 0
     child_runs: int = 0
     parent_unpruned_runs: int = 0
+
+
+@dataclass
+class WriteBatchStats:
+    input_ops: int = 0
+    output_records: int = 0
+    superseded: int = 0
+    puts: int = 0
+    removes: int = 0
+    key_bytes: int = 0
+    value_bytes: int = 0
 
 
 class RrdbLib:
@@ -272,6 +295,12 @@ class RrdbLib:
             L.rrdb_split.restype = C.c_int32
             L.rrdb_split.argtypes = [
                 C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(_SplitStats)]
+        self.has_write_batch = hasattr(L, "rrdb_write_batch")
+        if self.has_write_batch:
+            L.rrdb_write_batch.restype = C.c_int32
+            L.rrdb_write_batch.argtypes = [
+                C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(_WriteBatchStats)]
 
     @property
     def backend(self) -> str:
@@ -673,3 +702,44 @@ class RrdbPartition:
         err = self._L.rrdb_split(self._h, child._h, new_partition_count, C.byref(st))
         stats = SplitStats(**{f[0]: getattr(st, f[0]) for f in _SplitStats._fields_})
         return err, stats
+
+    # ---- batched writes: engine-only (include/rrdb_engine_ext.h) ----
+    def _need_write_batch(self):
+        if not self.lib.has_write_batch:
+            raise RuntimeError(
+                f"write_batch: backend {self.lib.backend!r} ({self.lib.path}) does not export "
+                "rrdb_write_batch (engine-only extension)")
+
+    def write_batch_arrays(self, keys_u8, key_offs_u64, vals_u8, val_offs_u64, expire_u32,
+                           kinds_u8, epoch_now: int = 0):
+        """write_batch from packed numpy arrays (no python loop; the bench and
+        the rejection tests, which hand in malformed arrays, use it)."""
+        import numpy as np
+
+        self._need_write_batch()
+        for a, dt in ((keys_u8, np.uint8), (key_offs_u64, np.uint64), (vals_u8, np.uint8),
+                      (val_offs_u64, np.uint64), (expire_u32, np.uint32), (kinds_u8, np.uint8)):
+            assert a.dtype == dt and a.flags["C_CONTIGUOUS"], (a.dtype, dt)
+        st = _WriteBatchStats()
+        err = self._L.rrdb_write_batch(
+            self._h, len(kinds_u8),
+            keys_u8.ctypes.data_as(C.c_void_p), key_offs_u64.ctypes.data_as(C.c_void_p),
+            vals_u8.ctypes.data_as(C.c_void_p), val_offs_u64.ctypes.data_as(C.c_void_p),
+            expire_u32.ctypes.data_as(C.c_void_p), kinds_u8.ctypes.data_as(C.c_void_p),
+            epoch_now, C.byref(st))
+        stats = WriteBatchStats(**{f[0]: getattr(st, f[0]) for f in _WriteBatchStats._fields_})
+        return err, stats
+
+    def write_batch(self, ops, epoch_now: int = 0):
+        """Apply `ops`, a list of (full_key, value_or_None, expire_ts) in
+        commit order (None = remove; duplicate keys allowed, the last op on a
+        key wins), as one new run sorted and deduplicated on the device.
+        Returns (err, WriteBatchStats)."""
+        import numpy as np
+
+        self._need_write_batch()
+        keys, koffs = _pack([o[0] for o in ops])
+        vals, voffs = _pack([o[1] if o[1] is not None else b"" for o in ops])
+        expire = np.array([o[2] if o[1] is not None else 0 for o in ops], dtype=np.uint32)
+        kinds = np.array([0 if o[1] is not None else 1 for o in ops], dtype=np.uint8)
+        return self.write_batch_arrays(keys, koffs, vals, voffs, expire, kinds, epoch_now)

@@ -27,6 +27,7 @@
 #include "../../include/rrdb_engine.h"
 #include "../../include/rrdb_engine_ext.h"
 #include "engine_common.h"
+#include "wb_stage.h"
 
 /* ---- launchers (kernels.hip) ---- */
 void launch_crc64_table_init(const uint64_t *host_table);
@@ -131,8 +132,18 @@ void launch_split_scatter(const uint8_t *, const uint64_t *, const uint8_t *, co
                           uint64_t *, uint64_t *, uint64_t *, hipStream_t);
 void launch_split_copy(const uint64_t *, const uint64_t *, uint64_t, uint64_t, uint64_t,
                        uint64_t *, uint8_t *, hipStream_t);
+int launch_wb_sort(const WbKeys &, uint64_t, uint32_t *, uint64_t *, uint32_t *, uint64_t *,
+                   uint32_t *, hipStream_t);
+void launch_wb_flags(const WbKeys &, const uint64_t *, uint64_t, const uint8_t *, uint64_t,
+                     const uint64_t *, const uint32_t *, uint64_t *, uint64_t *, uint64_t *,
+                     uint64_t *, hipStream_t);
+void launch_wb_scatter(const WbKeys &, const uint8_t *, const uint64_t *, uint64_t,
+                       const uint8_t *, uint64_t, const uint32_t *, const uint64_t *,
+                       const uint64_t *, const uint64_t *, const uint64_t *, uint64_t, uint64_t,
+                       uint64_t, uint64_t, uint64_t *, uint64_t *, uint64_t *, uint64_t *,
+                       uint64_t *, hipStream_t);
 
-#define HIP_OK(x)                                                                                  \
+#define HIP_OK(x)                                                                                 \
     do {                                                                                           \
         hipError_t e_ = (x);                                                                       \
         if (e_ != hipSuccess) {                                                                    \
@@ -3847,6 +3858,224 @@ int32_t rrdb_flush(void *h)
     auto *e = (HipEngine *)h;
     std::lock_guard<std::mutex> g(e->mu);
     return engine_flush(e);
+}
+
+} /* extern "C" */
+
+/* ---- batched writes (rrdb_write_batch, include/rrdb_engine_ext.h) ----
+ * The host validates, stages the values (wb_stage.h) and uploads once; the
+ * device sorts, dedups and emits the run (kernels.hip, "write batch").  Every
+ * buffer proportional to the batch is a plain try allocation owned by WbBufs:
+ * the scratch arena aborts when it has to grow, and a full device must come
+ * back as kIOError. */
+struct WbBufs {
+    std::vector<void *> dev;
+    std::vector<void *> host;
+    bool ok = true;
+    template <typename T> T *get(uint64_t bytes)
+    {
+        void *q = nullptr;
+        if (!ok)
+            return nullptr;
+        if (hipMalloc(&q, bytes ? bytes : 1) != hipSuccess) {
+            (void)hipGetLastError();
+            ok = false;
+            return nullptr;
+        }
+        dev.push_back(q);
+        return (T *)q;
+    }
+    template <typename T> T *get_host(uint64_t bytes)
+    {
+        void *q = ok ? malloc(bytes ? bytes : 1) : nullptr;
+        if (!q) {
+            ok = false;
+            return nullptr;
+        }
+        host.push_back(q);
+        return (T *)q;
+    }
+    bool upload(void *dst, const void *src, uint64_t bytes)
+    {
+        if (!ok || !bytes)
+            return ok;
+        if (hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipGetLastError();
+            ok = false;
+        }
+        return ok;
+    }
+    ~WbBufs()
+    {
+        for (void *q : dev)
+            (void)hipFree(q);
+        for (void *q : host)
+            free(q);
+    }
+};
+
+extern "C" {
+
+int32_t rrdb_write_batch(void *h, uint64_t n_ops, const uint8_t *keys, const uint64_t *key_offs,
+                         const uint8_t *values, const uint64_t *val_offs,
+                         const uint32_t *expire_ts, const uint8_t *kinds, uint32_t epoch_now,
+                         rrdb_write_batch_stats *stats)
+{
+    if (stats)
+        *stats = rrdb_write_batch_stats{};
+    if (!h)
+        return RRDB_INVALID_ARGUMENT;
+    auto *e = (HipEngine *)h;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (n_ops == 0)
+        return RRDB_OK;
+    using clk = std::chrono::steady_clock;
+    auto ms_since = [](clk::time_point t0) {
+        return std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+    };
+    const auto t_host = clk::now();
+    if (e->pend.active || e->pend_scan.active)
+        return RRDB_INVALID_ARGUMENT;
+    if (!wb_validate(n_ops, keys, key_offs, values, val_offs, kinds))
+        return RRDB_INVALID_ARGUMENT;
+    const uint64_t n = n_ops;
+    uint64_t sv_bytes = 0;
+    if (!wb_staged_bytes(n, val_offs, kinds, e->data_version, &sv_bytes))
+        return RRDB_INVALID_ARGUMENT;
+
+    /* pending memtable entries are older than the batch: their own run first */
+    e->activate();
+    int32_t rc = engine_flush(e);
+    if (rc != RRDB_OK)
+        return rc;
+
+    /* staging: keys verbatim, values with the header in front of every PUT */
+    WbBufs b;
+    uint8_t *h_svals = b.get_host<uint8_t>(sv_bytes);
+    uint64_t *h_svoff = b.get_host<uint64_t>((n + 1) * 8);
+    if (!b.ok)
+        return RRDB_IO_ERROR;
+    wb_stage_values(n, values, val_offs, expire_ts, kinds, e->data_version, e->default_ttl,
+                    epoch_now, h_svals, h_svoff);
+    const uint64_t in_fk = wb_fixed_stride(key_offs, n), in_fv = wb_fixed_stride(h_svoff, n);
+    const uint64_t in_kbytes = key_offs[n];
+    e->phase_ms["wb_stage"] = ms_since(t_host);
+
+    const auto t_up = clk::now();
+    uint8_t *d_keys = b.get<uint8_t>(in_kbytes);
+    uint64_t *d_koff = in_fk ? nullptr : b.get<uint64_t>((n + 1) * 8);
+    uint8_t *d_svals = b.get<uint8_t>(sv_bytes);
+    uint64_t *d_svoff = in_fv ? nullptr : b.get<uint64_t>((n + 1) * 8);
+    uint8_t *d_kinds = b.get<uint8_t>(n);
+    uint32_t *d_lcp = b.get<uint32_t>(256);
+    uint64_t *d_w0 = b.get<uint64_t>(n * 8), *d_w1 = b.get<uint64_t>(n * 8);
+    uint32_t *d_i0 = b.get<uint32_t>(n * 4), *d_i1 = b.get<uint32_t>(n * 4);
+    uint64_t *d_keep = b.get<uint64_t>(n * 8), *d_rank = b.get<uint64_t>(n * 8);
+    uint64_t *d_psc = b.get<uint64_t>(psum_scratch_elems(n) * 8);
+    uint64_t *d_ksz = in_fk ? nullptr : b.get<uint64_t>(n * 8);
+    uint64_t *d_kpos = in_fk ? nullptr : b.get<uint64_t>(n * 8);
+    uint64_t *d_vsz = in_fv ? nullptr : b.get<uint64_t>(n * 8);
+    uint64_t *d_vpos = in_fv ? nullptr : b.get<uint64_t>(n * 8);
+    uint64_t *d_red = b.get<uint64_t>(WBR_WORDS * 8);
+    b.upload(d_keys, keys, in_kbytes);
+    if (d_koff)
+        b.upload(d_koff, key_offs, (n + 1) * 8);
+    b.upload(d_svals, h_svals, sv_bytes);
+    if (d_svoff)
+        b.upload(d_svoff, h_svoff, (n + 1) * 8);
+    b.upload(d_kinds, kinds, n);
+    if (!b.ok)
+        return RRDB_IO_ERROR;
+    e->phase_ms["wb_upload"] = ms_since(t_up);
+
+    hipEvent_t ev[4];
+    for (auto &x : ev)
+        HIP_OK(hipEventCreate(&x));
+    auto drop_events = [&] {
+        for (auto &x : ev)
+            (void)hipEventDestroy(x);
+    };
+    const WbKeys wk{d_keys, d_koff, in_fk, d_lcp};
+    HIP_OK(hipEventRecord(ev[0], e->stream));
+    const int cur = launch_wb_sort(wk, n, d_lcp, d_w0, d_i0, d_w1, d_i1, e->stream);
+    const uint64_t *d_w = cur ? d_w1 : d_w0;
+    const uint32_t *d_ix = cur ? d_i1 : d_i0;
+    HIP_OK(hipEventRecord(ev[1], e->stream));
+
+    /* keep flags, rank, byte offsets; then the one read-back */
+    launch_wb_flags(wk, d_svoff, in_fv, d_kinds, n, d_w, d_ix, d_keep, d_ksz, d_vsz, d_red,
+                    e->stream);
+    launch_psum(d_keep, d_rank, n, d_psc, e->stream);
+    uint64_t tot[6] = {0, 0, 0, 0, 0, 0}, red[WBR_WORDS];
+    HIP_OK(hipMemcpyAsync(&tot[0], d_rank + n - 1, 8, hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipMemcpyAsync(&tot[1], d_keep + n - 1, 8, hipMemcpyDeviceToHost, e->stream));
+    if (!in_fk) {
+        launch_psum(d_ksz, d_kpos, n, d_psc, e->stream);
+        HIP_OK(hipMemcpyAsync(&tot[2], d_kpos + n - 1, 8, hipMemcpyDeviceToHost, e->stream));
+        HIP_OK(hipMemcpyAsync(&tot[3], d_ksz + n - 1, 8, hipMemcpyDeviceToHost, e->stream));
+    }
+    if (!in_fv) {
+        launch_psum(d_vsz, d_vpos, n, d_psc, e->stream);
+        HIP_OK(hipMemcpyAsync(&tot[4], d_vpos + n - 1, 8, hipMemcpyDeviceToHost, e->stream));
+        HIP_OK(hipMemcpyAsync(&tot[5], d_vsz + n - 1, 8, hipMemcpyDeviceToHost, e->stream));
+    }
+    HIP_OK(hipMemcpyAsync(red, d_red, sizeof(red), hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipStreamSynchronize(e->stream));
+    const uint64_t n_out = tot[0] + tot[1];
+    const uint64_t kbytes = in_fk ? n_out * in_fk : tot[2] + tot[3];
+    const uint64_t vbytes = in_fv ? n_out * in_fv : tot[4] + tot[5];
+
+    RunBuf r;
+    uint64_t *d_row_ksrc = b.get<uint64_t>(n_out * 8), *d_row_vsrc = b.get<uint64_t>(n_out * 8);
+    uint64_t *d_kanch = b.get<uint64_t>((((kbytes + 15) >> 10) + 2) * 8);
+    uint64_t *d_vanch = b.get<uint64_t>((((vbytes + 15) >> 10) + 2) * 8);
+    if (!b.ok || !e->alloc_base(r, n_out, kbytes, vbytes, RunAlloc::Try)) {
+        drop_events();
+        return RRDB_IO_ERROR;
+    }
+    /* the strides detect_fixed_* would report for the emitted run */
+    auto u32_or_0 = [](uint64_t v) { return v > UINT32_MAX ? 0u : (uint32_t)v; };
+    r.fixed_klen = red[WBR_KMIN] == red[WBR_KMAX] ? u32_or_0(red[WBR_KMIN]) : 0;
+    r.fixed_vlen = red[WBR_VMIN] == red[WBR_VMAX] ? u32_or_0(red[WBR_VMIN]) : 0;
+    r.fixed_vlen_put =
+        red[WBR_PUTS] && red[WBR_PVMIN] == red[WBR_PVMAX] ? u32_or_0(red[WBR_PVMIN]) : 0;
+    HIP_OK(hipEventRecord(ev[2], e->stream));
+    launch_wb_scatter(wk, d_svals, d_svoff, in_fv, d_kinds, n, d_ix, d_keep, d_rank, d_kpos,
+                      d_vpos, e->next_seq_floor, n_out, kbytes, vbytes, r.koff, r.voff, r.sk,
+                      d_row_ksrc, d_row_vsrc, e->stream);
+    launch_split_copy(d_row_ksrc, r.koff, n_out, r.fixed_klen, kbytes, d_kanch, r.keys,
+                      e->stream);
+    launch_split_copy(d_row_vsrc, r.voff, n_out, r.fixed_vlen, vbytes, d_vanch, r.vals,
+                      e->stream);
+    HIP_OK(hipEventRecord(ev[3], e->stream));
+    if (!e->finish_run(r, nullptr, RunAlloc::Try, e->bloom_enabled)) {
+        e->free_run(r);
+        drop_events();
+        return RRDB_IO_ERROR;
+    }
+    float ms = 0, ms2 = 0;
+    if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
+        e->phase_ms["wb_sort"] = ms;
+    if (hipEventElapsedTime(&ms, ev[1], ev[2]) == hipSuccess &&
+        hipEventElapsedTime(&ms2, ev[2], ev[3]) == hipSuccess)
+        e->phase_ms["wb_emit"] = ms + ms2;
+    if (hipEventElapsedTime(&ms, ev[0], ev[3]) == hipSuccess)
+        e->phase_ms["wb_total"] = ms;
+    drop_events();
+
+    e->runs.push_back(r);
+    e->runs_changed();
+    e->next_seq_floor += n;
+    if (stats) {
+        stats->input_ops = n;
+        stats->output_records = n_out;
+        stats->superseded = n - n_out;
+        stats->puts = red[WBR_PUTS];
+        stats->removes = n_out - red[WBR_PUTS];
+        stats->key_bytes = kbytes;
+        stats->value_bytes = vbytes;
+    }
+    return RRDB_OK;
 }
 
 } /* extern "C" */

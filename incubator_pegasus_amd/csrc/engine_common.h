@@ -30,6 +30,25 @@
 #define GRP_CAP 2048
 #define GRP_TARGET 1024
 
+/* write batch (rrdb_write_batch): (word, op index) pairs one workgroup sorts
+ * in LDS, and the output slice one workgroup merges per pass.  2048 pairs are
+ * 24 KiB (u64 words + u32 indices), so six workgroups fit a CU's 160 KiB. */
+#define WB_TILE 2048
+
+/* device view of a staged write batch: what the sort's comparator needs to
+ * break a tie in the 8-byte word */
+struct WbKeys {
+    const uint8_t *keys;
+    const uint64_t *koff; /* n+1; null when every key is `fk` bytes long */
+    uint64_t fk;
+    const uint32_t *lcp;  /* device: L, the prefix all keys share */
+};
+
+/* write-batch emit reduction (one block of u64 words, vector atomics) */
+enum {
+    WBR_KMIN = 0, WBR_KMAX, WBR_VMIN, WBR_VMAX, WBR_PVMIN, WBR_PVMAX, WBR_PUTS, WBR_WORDS
+};
+
 /* device-visible descriptor of one sorted run */
 struct DevRun {
     const uint8_t *keys;

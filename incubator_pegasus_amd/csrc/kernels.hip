@@ -3607,3 +3607,390 @@ void launch_split_copy(const uint64_t *d_row_src, const uint64_t *d_row_off, uin
             d_row_off, d_row_src, n_rows, bytes, d_anchor, anch, d_out);
     }
 }
+
+/* ================= write batch (rrdb_write_batch) =================
+ * An unsorted batch of ops (commit order, duplicate keys allowed) becomes the
+ * run put/remove x N + flush would have built: sort by (key asc, op index
+ * desc), keep the first of every equal-key group.
+ *   prefix:  L = min_i lcp(key_i, key_0); every key is >= L bytes long.
+ *   word:    w_i = big-endian u64 of key bytes [L, L+8), zero-padded.  The
+ *            sort moves (w_i, i) pairs; key bytes are read again only when
+ *            two words tie.
+ *   tile:    one workgroup sorts WB_TILE pairs in LDS (bitonic network, in
+ *            place, padded to the next power of two with a maximal pad).
+ *   merge:   ceil(log2(tiles)) passes between two pair arrays.  A workgroup
+ *            owns one WB_TILE slice of the output, finds its two input
+ *            sub-ranges by a merge-path diagonal search in global memory,
+ *            stages them in LDS, and every element finds its output slot by a
+ *            binary search in the other staged range.  A run without a
+ *            partner (odd tile out) has an empty B range and is copied.
+ *   flags:   position p is kept iff its key differs from position p-1's;
+ *            launch_psum ranks the kept ones.
+ *   emit:    scatter sk / offsets / source addresses by rank, then the
+ *            split's chunk copies (launch_split_copy) move the bytes.
+ * wb_less is the one ordering every stage uses; it is strict and total, so
+ * the result does not depend on the grid or on scheduling. */
+#define WB_PAD 0xFFFFFFFFu
+
+__device__ static inline const uint8_t *wb_key(const WbKeys &k, uint64_t i, uint64_t *len)
+{
+    if (k.fk) {
+        *len = k.fk;
+        return k.keys + i * k.fk;
+    }
+    uint64_t o = k.koff[i];
+    *len = k.koff[i + 1] - o;
+    return k.keys + o;
+}
+
+__device__ static inline uint64_t wb_word(const uint8_t *p, uint64_t len, uint64_t L)
+{
+    uint64_t w = 0;
+    if (L + 8 <= len) {
+        __builtin_memcpy(&w, p + L, 8);
+        return __builtin_bswap64(w);
+    }
+    for (uint64_t j = 0; j < 8; j++) {
+        w <<= 8;
+        if (L + j < len)
+            w |= p[L + j];
+    }
+    return w;
+}
+
+/* order of two ops whose words tie: the bytes from L+8 on, then the true
+ * lengths (zero padding makes "ab" and "ab\0" tie in the word) */
+__device__ static inline int wb_tail_cmp(const WbKeys &k, uint64_t L, uint32_t ia, uint32_t ib)
+{
+    uint64_t la, lb;
+    const uint8_t *pa = wb_key(k, ia, &la);
+    const uint8_t *pb = wb_key(k, ib, &lb);
+    uint64_t sa = la < L + 8 ? la : L + 8;
+    uint64_t sb = lb < L + 8 ? lb : L + 8;
+    int c = dev_key_cmp(pa + sa, la - sa, pb + sb, lb - sb);
+    if (c)
+        return c;
+    return la < lb ? -1 : (la > lb ? 1 : 0);
+}
+
+/* (key asc, op index desc); the pad (w = ~0, index WB_PAD) is the maximum */
+__device__ static inline bool wb_less(const WbKeys &k, uint64_t L, uint64_t wa, uint32_t ia,
+                                      uint64_t wb, uint32_t ib)
+{
+    if (wa != wb)
+        return wa < wb;
+    if (ia == WB_PAD || ib == WB_PAD)
+        return ia != WB_PAD;
+    if (ia == ib)
+        return false;
+    int c = wb_tail_cmp(k, L, ia, ib);
+    if (c)
+        return c < 0;
+    return ia > ib;
+}
+
+/* *lcp (preset to ~0) = min over ops of lcp(key_i, key_0): block minimum in
+ * LDS, then one atomicMin per block */
+__global__ void __launch_bounds__(BLOCK) k_wb_lcp(WbKeys k, uint64_t n, uint32_t *lcp)
+{
+    __shared__ uint32_t s_min;
+    uint64_t l0;
+    const uint8_t *k0 = wb_key(k, 0, &l0);
+    uint32_t best = l0 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)l0;
+    if (threadIdx.x == 0)
+        s_min = best;
+    __syncthreads();
+    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n && best;
+         i += gridDim.x * (uint64_t)blockDim.x) {
+        uint64_t len;
+        const uint8_t *p = wb_key(k, i, &len);
+        uint32_t m = len < best ? (uint32_t)len : best;
+        uint32_t j = 0;
+        while (j < m && p[j] == k0[j])
+            j++;
+        best = j;
+    }
+    atomicMin(&s_min, best);
+    __syncthreads();
+    if (threadIdx.x == 0)
+        atomicMin(lcp, s_min);
+}
+
+/* tile t = ops [t*WB_TILE, ...) sorted into ow/oi at the same positions */
+__global__ void __launch_bounds__(BLOCK)
+    k_wb_tile_sort(WbKeys k, uint64_t n, uint64_t *ow, uint32_t *oi)
+{
+    __shared__ uint64_t sw[WB_TILE];
+    __shared__ uint32_t si[WB_TILE];
+    const uint64_t L = *k.lcp;
+    for (uint64_t tile = blockIdx.x; tile * WB_TILE < n; tile += gridDim.x) {
+        const uint64_t base = tile * WB_TILE;
+        const uint32_t cnt = n - base < WB_TILE ? (uint32_t)(n - base) : WB_TILE;
+        uint32_t P = 2;
+        while (P < cnt)
+            P <<= 1;
+        for (uint32_t e = threadIdx.x; e < P; e += BLOCK) {
+            if (e < cnt) {
+                uint64_t len;
+                const uint8_t *p = wb_key(k, base + e, &len);
+                sw[e] = wb_word(p, len, L);
+                si[e] = (uint32_t)(base + e);
+            } else {
+                sw[e] = ~0ull;
+                si[e] = WB_PAD;
+            }
+        }
+        __syncthreads();
+        for (uint32_t kk = 2; kk <= P; kk <<= 1) {
+            for (uint32_t j = kk >> 1; j > 0; j >>= 1) {
+                for (uint32_t t = threadIdx.x; t < P / 2; t += BLOCK) {
+                    uint32_t lo = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+                    uint32_t hi = lo + j;
+                    uint64_t wa = sw[lo], wb = sw[hi];
+                    uint32_t ia = si[lo], ib = si[hi];
+                    bool asc = (lo & kk) == 0;
+                    bool swap = asc ? wb_less(k, L, wb, ib, wa, ia) : wb_less(k, L, wa, ia, wb, ib);
+                    if (swap) {
+                        sw[lo] = wb;
+                        si[lo] = ib;
+                        sw[hi] = wa;
+                        si[hi] = ia;
+                    }
+                }
+                __syncthreads();
+            }
+        }
+        for (uint32_t e = threadIdx.x; e < cnt; e += BLOCK) {
+            ow[base + e] = sw[e];
+            oi[base + e] = si[e];
+        }
+        __syncthreads();
+    }
+}
+
+/* how many of the first d merged elements come from A = [a_beg, +lenA),
+ * the rest from B = [b_beg, +lenB) */
+__device__ static inline uint64_t wb_merge_path(const WbKeys &k, uint64_t L, const uint64_t *w,
+                                                const uint32_t *ix, uint64_t a_beg,
+                                                uint64_t lenA, uint64_t b_beg, uint64_t lenB,
+                                                uint64_t d)
+{
+    uint64_t lo = d > lenB ? d - lenB : 0, hi = d < lenA ? d : lenA;
+    while (lo < hi) {
+        uint64_t mid = (lo + hi) >> 1;
+        uint64_t ua = a_beg + mid, ub = b_beg + (d - 1 - mid);
+        if (wb_less(k, L, w[ua], ix[ua], w[ub], ix[ub]))
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+/* one pass: sorted runs of `width` pairs merge two and two into ow/oi */
+__global__ void __launch_bounds__(BLOCK)
+    k_wb_merge(WbKeys k, uint64_t n, uint64_t width, const uint64_t *iw, const uint32_t *ii,
+               uint64_t *ow, uint32_t *oi)
+{
+    __shared__ uint64_t sw[WB_TILE];
+    __shared__ uint32_t si[WB_TILE];
+    __shared__ uint64_t s_cut[2];
+    const uint64_t L = *k.lcp;
+    for (uint64_t slice = blockIdx.x; slice * WB_TILE < n; slice += gridDim.x) {
+        const uint64_t o = slice * WB_TILE;
+        const uint64_t pairw = 2 * width;
+        const uint64_t base = o / pairw * pairw;
+        const uint64_t a_end = base + width < n ? base + width : n;
+        const uint64_t b_end = base + pairw < n ? base + pairw : n;
+        const uint64_t lenA = a_end - base, lenB = b_end - a_end;
+        const uint64_t d0 = o - base;
+        const uint64_t d1 = d0 + WB_TILE < lenA + lenB ? d0 + WB_TILE : lenA + lenB;
+        if (threadIdx.x == 0)
+            s_cut[0] = wb_merge_path(k, L, iw, ii, base, lenA, a_end, lenB, d0);
+        if (threadIdx.x == WAVE)
+            s_cut[1] = wb_merge_path(k, L, iw, ii, base, lenA, a_end, lenB, d1);
+        __syncthreads();
+        const uint64_t a0 = s_cut[0], a1 = s_cut[1];
+        const uint64_t b0 = d0 - a0, b1 = d1 - a1;
+        if (a1 < a0 || b1 < b0 || a1 > lenA || b1 > lenB) {
+            __syncthreads(); /* cannot happen: wb_less is a strict total order */
+            continue;
+        }
+        const uint32_t na = (uint32_t)(a1 - a0), nb = (uint32_t)(b1 - b0);
+        for (uint32_t e = threadIdx.x; e < na; e += BLOCK) {
+            sw[e] = iw[base + a0 + e];
+            si[e] = ii[base + a0 + e];
+        }
+        for (uint32_t e = threadIdx.x; e < nb; e += BLOCK) {
+            sw[na + e] = iw[a_end + b0 + e];
+            si[na + e] = ii[a_end + b0 + e];
+        }
+        __syncthreads();
+        for (uint32_t e = threadIdx.x; e < na + nb; e += BLOCK) {
+            const uint64_t w = sw[e];
+            const uint32_t i = si[e];
+            /* my slot = my position in my range + the others below me */
+            const uint32_t first = e < na ? na : 0, last = e < na ? na + nb : na;
+            uint32_t lb = first, ub = last;
+            while (lb < ub) {
+                uint32_t mid = (lb + ub) >> 1;
+                if (wb_less(k, L, sw[mid], si[mid], w, i))
+                    lb = mid + 1;
+                else
+                    ub = mid;
+            }
+            const uint32_t pos = (e < na ? e : e - na) + (lb - first);
+            ow[o + pos] = w;
+            oi[o + pos] = i;
+        }
+        __syncthreads();
+    }
+}
+
+/* keep[p] = 1 iff sorted position p holds the newest op of its key; its key
+ * and encoded-value sizes (0 when dropped) for the byte-offset scans (a null
+ * output = that column is fixed-stride); and the kept rows' length min/max,
+ * PUT count and PUT-value min/max into red[WBR_*] */
+__global__ void __launch_bounds__(BLOCK)
+    k_wb_flags(WbKeys k, const uint64_t *svoff, uint64_t fv, const uint8_t *kinds, uint64_t n,
+               const uint64_t *w, const uint32_t *ix, uint64_t *keep, uint64_t *ksz,
+               uint64_t *vsz, unsigned long long *red)
+{
+    __shared__ unsigned long long s_red[WBR_WORDS];
+    if (threadIdx.x < WBR_WORDS)
+        s_red[threadIdx.x] = (threadIdx.x == WBR_KMIN || threadIdx.x == WBR_VMIN ||
+                              threadIdx.x == WBR_PVMIN)
+                                 ? ~0ull
+                                 : 0ull;
+    __syncthreads();
+    const uint64_t L = *k.lcp;
+    unsigned long long kmin = ~0ull, kmax = 0, vmin = ~0ull, vmax = 0, pvmin = ~0ull, pvmax = 0,
+                       puts = 0;
+    for (uint64_t p = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; p < n;
+         p += gridDim.x * (uint64_t)blockDim.x) {
+        const uint32_t i = ix[p];
+        bool kept = p == 0 || w[p] != w[p - 1] || wb_tail_cmp(k, L, ix[p - 1], i) != 0;
+        uint64_t kl;
+        (void)wb_key(k, i, &kl);
+        const uint64_t vl = fv ? fv : svoff[i + 1] - svoff[i];
+        keep[p] = kept ? 1 : 0;
+        if (ksz)
+            ksz[p] = kept ? kl : 0;
+        if (vsz)
+            vsz[p] = kept ? vl : 0;
+        if (kept) {
+            kmin = kl < kmin ? kl : kmin;
+            kmax = kl > kmax ? kl : kmax;
+            vmin = vl < vmin ? vl : vmin;
+            vmax = vl > vmax ? vl : vmax;
+            if (kinds[i] == 0) {
+                puts++;
+                pvmin = vl < pvmin ? vl : pvmin;
+                pvmax = vl > pvmax ? vl : pvmax;
+            }
+        }
+    }
+    if (kmax) { /* this thread kept a row (keys are at least 2 bytes) */
+        atomicMin(&s_red[WBR_KMIN], kmin);
+        atomicMax(&s_red[WBR_KMAX], kmax);
+        atomicMin(&s_red[WBR_VMIN], vmin);
+        atomicMax(&s_red[WBR_VMAX], vmax);
+        if (puts) {
+            atomicMin(&s_red[WBR_PVMIN], pvmin);
+            atomicMax(&s_red[WBR_PVMAX], pvmax);
+            atomicAdd(&s_red[WBR_PUTS], puts);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < WBR_WORDS) {
+        const unsigned long long v = s_red[threadIdx.x];
+        if (threadIdx.x == WBR_KMIN || threadIdx.x == WBR_VMIN || threadIdx.x == WBR_PVMIN)
+            atomicMin(&red[threadIdx.x], v);
+        else if (threadIdx.x == WBR_PUTS)
+            atomicAdd(&red[threadIdx.x], v);
+        else
+            atomicMax(&red[threadIdx.x], v);
+    }
+}
+
+/* the kept ops, by rank: osk, 0-based okoff/ovoff (n_out+1 entries) and the
+ * per-row source addresses the chunk copies read.  fk / fv != 0: the offset
+ * is rank x stride; else kpos / vpos hold it. */
+__global__ void __launch_bounds__(BLOCK)
+    k_wb_scatter(WbKeys k, const uint8_t *svals, const uint64_t *svoff, uint64_t fv,
+                 const uint8_t *kinds, uint64_t n, const uint32_t *ix, const uint64_t *keep,
+                 const uint64_t *rank, const uint64_t *kpos, const uint64_t *vpos,
+                 uint64_t seq_floor, uint64_t n_out, uint64_t kbytes, uint64_t vbytes,
+                 uint64_t *okoff, uint64_t *ovoff, uint64_t *osk, uint64_t *row_ksrc,
+                 uint64_t *row_vsrc)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        okoff[n_out] = kbytes;
+        ovoff[n_out] = vbytes;
+    }
+    for (uint64_t p = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; p < n;
+         p += gridDim.x * (uint64_t)blockDim.x) {
+        if (!keep[p])
+            continue;
+        const uint64_t r = rank[p];
+        if (r >= n_out)
+            continue; /* cannot happen: n_out is this scan's total */
+        const uint64_t i = ix[p];
+        osk[r] = ((seq_floor + i) << 1) | (uint64_t)(kinds[i] & 1);
+        okoff[r] = k.fk ? r * k.fk : kpos[p];
+        ovoff[r] = fv ? r * fv : vpos[p];
+        row_ksrc[r] = (uint64_t)(k.keys + (k.fk ? i * k.fk : k.koff[i]));
+        row_vsrc[r] = (uint64_t)(svals + (fv ? i * fv : svoff[i]));
+    }
+}
+
+static inline uint32_t wb_tile_grid(uint64_t n)
+{
+    uint64_t t = (n + WB_TILE - 1) / WB_TILE;
+    return (uint32_t)(t > (1u << 20) ? (1u << 20) : (t ? t : 1));
+}
+
+/* sort the batch's (word, index) pairs; d_lcp is 4 bytes of scratch that
+ * k.lcp points at.  Returns 0 / 1: the result is in (w0, i0) / (w1, i1). */
+int launch_wb_sort(const WbKeys &k, uint64_t n, uint32_t *d_lcp, uint64_t *d_w0, uint32_t *d_i0,
+                   uint64_t *d_w1, uint32_t *d_i1, hipStream_t s)
+{
+    HIP_CHECK(hipMemsetAsync(d_lcp, 0xFF, 4, s));
+    k_wb_lcp<<<grid_for(n, BLOCK), BLOCK, 0, s>>>(k, n, d_lcp);
+    k_wb_tile_sort<<<wb_tile_grid(n), BLOCK, 0, s>>>(k, n, d_w0, d_i0);
+    int cur = 0;
+    for (uint64_t width = WB_TILE; width < n; width *= 2) {
+        if (cur == 0)
+            k_wb_merge<<<wb_tile_grid(n), BLOCK, 0, s>>>(k, n, width, d_w0, d_i0, d_w1, d_i1);
+        else
+            k_wb_merge<<<wb_tile_grid(n), BLOCK, 0, s>>>(k, n, width, d_w1, d_i1, d_w0, d_i0);
+        cur ^= 1;
+    }
+    return cur;
+}
+
+/* d_red: WBR_WORDS u64 words, initialised here */
+void launch_wb_flags(const WbKeys &k, const uint64_t *d_svoff, uint64_t fv,
+                     const uint8_t *d_kinds, uint64_t n, const uint64_t *d_w,
+                     const uint32_t *d_ix, uint64_t *d_keep, uint64_t *d_ksz, uint64_t *d_vsz,
+                     uint64_t *d_red, hipStream_t s)
+{
+    uint64_t init[WBR_WORDS];
+    for (int j = 0; j < WBR_WORDS; j++)
+        init[j] = (j == WBR_KMIN || j == WBR_VMIN || j == WBR_PVMIN) ? ~0ull : 0ull;
+    HIP_CHECK(hipMemcpyAsync(d_red, init, sizeof(init), hipMemcpyHostToDevice, s));
+    k_wb_flags<<<grid_for(n, BLOCK), BLOCK, 0, s>>>(k, d_svoff, fv, d_kinds, n, d_w, d_ix, d_keep,
+                                                   d_ksz, d_vsz, (unsigned long long *)d_red);
+}
+
+void launch_wb_scatter(const WbKeys &k, const uint8_t *d_svals, const uint64_t *d_svoff,
+                       uint64_t fv, const uint8_t *d_kinds, uint64_t n, const uint32_t *d_ix,
+                       const uint64_t *d_keep, const uint64_t *d_rank, const uint64_t *d_kpos,
+                       const uint64_t *d_vpos, uint64_t seq_floor, uint64_t n_out,
+                       uint64_t kbytes, uint64_t vbytes, uint64_t *d_okoff, uint64_t *d_ovoff,
+                       uint64_t *d_osk, uint64_t *d_row_ksrc, uint64_t *d_row_vsrc, hipStream_t s)
+{
+    k_wb_scatter<<<grid_for(n, BLOCK), BLOCK, 0, s>>>(
+        k, d_svals, d_svoff, fv, d_kinds, n, d_ix, d_keep, d_rank, d_kpos, d_vpos, seq_floor,
+        n_out, kbytes, vbytes, d_okoff, d_ovoff, d_osk, d_row_ksrc, d_row_vsrc);
+}

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Mixed-operation GPU stress: randomized interleavings of every C-ABI
-entry point on one handle — writes, flushes, point/range/batched reads with
+entry point on one handle — writes, batched writes (rrdb_write_batch, which
+the oracle replays through put/remove), flushes, point/range/batched reads with
 the serving lanes forced on, pipelined count scans, paged scans, real
 compactions, checkpoints and restores — cross-checked against the CPU
 oracle driven with the same operation stream.  Complements tools/soak.py
@@ -38,8 +39,32 @@ def main():
     tmp_o = tempfile.mkdtemp(prefix="stress_ckpt_o_")
     decree = 0
     for step in range(steps):
-        op = rnd.randrange(10)
-        if op <= 1:  # writes
+        op = rnd.randrange(11)
+        if op == 10:  # batched write: the engine sorts and dedups it on the
+            # device; the oracle takes the same ops one by one.  The batch
+            # flushes the memtable ahead of itself and ends in a run of its
+            # own, so the oracle flushes at those two points
+            ops = []
+            for _ in range(rnd.choice([1, 7, 300, 2049, 5000])):
+                k = D.generate_key(b"hk%03d" % rnd.randrange(60), b"s%02d" % rnd.randrange(6))
+                if rnd.random() < 0.15:
+                    ops.append((k, None, 0))
+                else:
+                    ops.append((k, b"b%d-%d" % (step, len(ops)),
+                                rnd.choice([0, 0, 0, now + 50])))
+            err, st = g.write_batch(ops, now)
+            assert err == OK and st.input_ops == len(ops)
+            assert o.flush() == OK
+            for k, v, ets in ops:
+                hk, sk = D.restore_key(k)
+                if v is None:
+                    o.remove(hk, sk)
+                else:
+                    o.put(hk, sk, v, ets, now)
+            assert o.flush() == OK
+            assert g.num_runs() == o.num_runs() and g.num_records() == o.num_records()
+            checks += 1
+        elif op <= 1:  # writes
             for _ in range(rnd.randrange(1, 25)):
                 hk = b"hk%03d" % rnd.randrange(60)
                 sk = b"s%02d" % rnd.randrange(6)
