@@ -99,6 +99,33 @@
  *     unchanged, and a memtable flush that already happened stays.
  *   - rrdb_phase_ms reports wb_sort, wb_emit and wb_total (device time), and
  *     wb_stage and wb_upload (host time of the staging and of the copies).
+ *
+ * Compaction route.  One compaction pass is a rank kernel followed by an emit
+ * kernel, and which pair runs is decided per pass: from the envs
+ * "engine.rank_mode" and "engine.emit_mode", the run count, the key shape of
+ * the runs (the tail-word kernels need one shared key stride >= 8 and a shared
+ * first stride-8 bytes) and whether the pass is a window.  Every pair produces
+ * the same run, so no read can tell them apart; rrdb_last_compact_route
+ * reports which pair the last pass took, so that a test or a benchmark that
+ * means one kernel can tell it ran that kernel.
+ *   - rank: RRDB_ROUTE_RANK_GLOBAL / _LDS / _LDST / _GRP, numbered as
+ *     engine.rank_mode numbers them.  A mode that does not apply (lds with a
+ *     non-chunked emit or a single run; ldst or grp on runs that are not
+ *     tail-word eligible; grp with more than 32 runs or the input-major
+ *     emit) falls to ldst when engine.rank_mode is ldst and the runs are
+ *     eligible, else to global.
+ *   - emit: RRDB_ROUTE_EMIT_RANK / _INPUT / _CHUNKED as engine.emit_mode
+ *     numbers them, and _CHUNKED_FIXED for the chunked emit in its
+ *     all-fixed-stride form (bottommost, one key stride and one PUT-value
+ *     stride across the runs).  A window pass always emits chunked.
+ *   - RRDB_ROUTE_NONE (-1): rank when the pass had no input record or no pass
+ *     has started on the handle; emit when nothing was emitted (no output
+ *     record), and between rrdb_manual_compact_begin and its finish.  Both
+ *     modes are read once, at the begin: an env set before the finish
+ *     applies to the next pass.
+ *   - Manual, window and auto passes all report.  A call that is rejected
+ *     before the pass starts leaves the previous report.  Recording costs no
+ *     device work and changes no behaviour.
  */
 #ifndef RRDB_ENGINE_EXT_H
 #define RRDB_ENGINE_EXT_H
@@ -180,6 +207,27 @@ int32_t rrdb_write_batch(void *h, uint64_t n_ops,
                          const uint8_t *values, const uint64_t *val_offs,
                          const uint32_t *expire_ts, const uint8_t *kinds,
                          uint32_t epoch_now, rrdb_write_batch_stats *stats);
+
+enum {
+    RRDB_ROUTE_NONE = -1,
+    RRDB_ROUTE_RANK_GLOBAL = 0, /* global searches + bound-table narrowing   */
+    RRDB_ROUTE_RANK_LDS = 1,    /* LDS-staged full-key block rank            */
+    RRDB_ROUTE_RANK_LDST = 3,   /* windowed LDS-staged tail-word rank        */
+    RRDB_ROUTE_RANK_GRP = 4,    /* group-streaming tail-word rank            */
+    RRDB_ROUTE_EMIT_RANK = 0,   /* rank-major waves                          */
+    RRDB_ROUTE_EMIT_INPUT = 1,  /* input-major waves                         */
+    RRDB_ROUTE_EMIT_CHUNKED = 2,       /* chunked, per-row sizes             */
+    RRDB_ROUTE_EMIT_CHUNKED_FIXED = 3  /* chunked, all-fixed-stride          */
+};
+
+typedef struct {
+    int32_t rank; /* RRDB_ROUTE_RANK_* or RRDB_ROUTE_NONE */
+    int32_t emit; /* RRDB_ROUTE_EMIT_* or RRDB_ROUTE_NONE */
+} rrdb_compact_route;
+
+/* The rank and emit kernels the handle's last compaction pass dispatched to;
+ * see the header comment.  Read-only.  kInvalidArgument: out == NULL. */
+int32_t rrdb_last_compact_route(void *h, rrdb_compact_route *out);
 
 #ifdef __cplusplus
 }

@@ -144,6 +144,16 @@ class _WriteBatchStats(C.Structure):
     ]
 
 
+class _CompactRoute(C.Structure):
+    _fields_ = [("rank", C.c_int32), ("emit", C.c_int32)]
+
+
+# rrdb_compact_route values (include/rrdb_engine_ext.h)
+ROUTE_NONE = -1
+ROUTE_RANK_GLOBAL, ROUTE_RANK_LDS, ROUTE_RANK_LDST, ROUTE_RANK_GRP = 0, 1, 3, 4
+ROUTE_EMIT_RANK, ROUTE_EMIT_INPUT, ROUTE_EMIT_CHUNKED, ROUTE_EMIT_CHUNKED_FIXED = 0, 1, 2, 3
+
+
 def _cslice(b: bytes, keep: list) -> _CSlice:
     """Build a _CSlice over a copy of b; the backing buffer is appended to
     `keep`, which the caller must hold alive across the C call (struct field
@@ -301,6 +311,10 @@ class RrdbLib:
             L.rrdb_write_batch.argtypes = [
                 C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                 C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(_WriteBatchStats)]
+        self.has_compact_route = hasattr(L, "rrdb_last_compact_route")
+        if self.has_compact_route:
+            L.rrdb_last_compact_route.restype = C.c_int32
+            L.rrdb_last_compact_route.argtypes = [C.c_void_p, C.POINTER(_CompactRoute)]
 
     @property
     def backend(self) -> str:
@@ -686,6 +700,20 @@ class RrdbPartition:
                                         C.byref(st))
         stats = CompactStats(**{f[0]: getattr(st, f[0]) for f in _CompactStats._fields_})
         return err, first.value, n.value, stats
+
+    # ---- compaction route: engine-only (include/rrdb_engine_ext.h) ----
+    def last_compact_route(self):
+        """(rank, emit) of the last compaction pass on this handle: the
+        ROUTE_RANK_* / ROUTE_EMIT_* values, ROUTE_NONE where no kernel ran."""
+        if not self.lib.has_compact_route:
+            raise RuntimeError(
+                f"last_compact_route: backend {self.lib.backend!r} ({self.lib.path}) does not "
+                "export rrdb_last_compact_route (engine-only extension)")
+        rt = _CompactRoute()
+        err = self._L.rrdb_last_compact_route(self._h, C.byref(rt))
+        if err != OK:
+            raise RuntimeError(f"rrdb_last_compact_route failed: status {err}")
+        return rt.rank, rt.emit
 
     # ---- partition split: engine-only (include/rrdb_engine_ext.h) ----
     def split(self, child: "RrdbPartition", new_partition_count: int):

@@ -685,7 +685,7 @@ struct HipEngine {
     struct PendingCompact {
         bool active = false, trivial = false, keep_inputs = false;
         /* the pass merges runs [first, first+R); bottommost iff first == 0 */
-        bool bottommost = true, chunked = false;
+        bool bottommost = true;
         size_t first = 0;
         int R = 0;
         uint64_t total = 0;
@@ -698,6 +698,10 @@ struct HipEngine {
         CompactStatsDev *d_stats = nullptr;
         uint64_t fk = 0, fv = 0; /* all-fixed-stride emit (ksz/vsz skipped) */
         bool no_rewrite = false;  /* changed/new_expire arrays skipped */
+        /* the emit the arrays above were built for: engine.emit_mode as
+         * phase 1 read it (chunked for a window), so that a set_envs between
+         * begin and finish cannot send them to another emit kernel */
+        int emit_mode = 2;
         hipEvent_t ev[6] = {};
         rrdb_compact_stats st{};
     } pend;
@@ -926,6 +930,10 @@ struct HipEngine {
                           0 = global searches + bound-table narrowing,
                           1 = LDS-staged full-key block rank
                           (env "engine.rank_mode": grp|ldst|global|lds) */
+    /* which kernels the last compaction pass dispatched to
+       (rrdb_last_compact_route): written at the branches of compact_begin /
+       compact_finish, read by nothing else */
+    rrdb_compact_route last_route{RRDB_ROUTE_NONE, RRDB_ROUTE_NONE};
     int split_crc_lds = 1; /* rrdb_split classify: crc64 table staged in LDS
                               once per workgroup (1, default) or read from
                               global memory (0) (env "engine.split_crc":
@@ -3089,6 +3097,7 @@ static int32_t compact_begin(HipEngine *e, const rrdb_compact_options *opts, uin
     if (!win && e->manual_compact_disabled)
         return RRDB_INVALID_ARGUMENT;
     e->activate();
+    e->last_route = {RRDB_ROUTE_NONE, RRDB_ROUTE_NONE};
     const size_t first = win ? win->first : 0;
     int R = (int)(win ? win->n : e->runs.size());
     const bool bottommost = first == 0;
@@ -3169,6 +3178,7 @@ static int32_t compact_begin(HipEngine *e, const rrdb_compact_options *opts, uin
     HIP_OK(hipMemsetAsync(d_stats, 0, 8 * sizeof(CompactStatsDev), e->stream));
     if (e->rank_mode == 1 && R > 1 && emit_mode == 2) {
         /* LDS-staged block rank: shift-8 bound table + per-run block counts */
+        e->last_route.rank = RRDB_ROUTE_RANK_LDS;
         uint64_t *d_bt8_off = nullptr, *d_bt8 = nullptr;
         {
             uint64_t *c_off = nullptr, *c_bt = nullptr;
@@ -3196,6 +3206,7 @@ static int32_t compact_begin(HipEngine *e, const rrdb_compact_options *opts, uin
         HIP_OK(hipEventRecord(ev[1], e->stream));
     } else if (R > 1 && emit_mode != 1 && e->grp_eligible(first, (size_t)R)) {
         /* group-streaming rank: no bound table; anchors partition the runs */
+        e->last_route.rank = RRDB_ROUTE_RANK_GRP;
         uint64_t *d_anch = nullptr;
         uint64_t n_groups = e->build_anchors(dr, R, lo, hi, d_lo, d_hi, &d_anch);
         HIP_OK(hipEventRecord(ev[0], e->stream));
@@ -3208,6 +3219,7 @@ static int32_t compact_begin(HipEngine *e, const rrdb_compact_options *opts, uin
         e->build_bound_table(dr, R, lo, hi, d_lo, d_hi, &d_bt_off, &d_bt);
     HIP_OK(hipEventRecord(ev[0], e->stream));
     bool ldst_ok = R > 1 && e->ldst_eligible(first, (size_t)R);
+    e->last_route.rank = ldst_ok ? RRDB_ROUTE_RANK_LDST : RRDB_ROUTE_RANK_GLOBAL;
     if (ldst_ok)
         launch_rank_compact_ldst(dr, R, d_lo, d_hi, d_wp, total, cp, d_order, d_keepw,
                                  d_changed, d_new_expire, d_ksz, d_vsz, d_rank_of, d_bt_off,
@@ -3246,7 +3258,7 @@ static int32_t compact_begin(HipEngine *e, const rrdb_compact_options *opts, uin
     e->pend.R = R;
     e->pend.first = first;
     e->pend.bottommost = bottommost;
-    e->pend.chunked = win != nullptr;
+    e->pend.emit_mode = emit_mode;
     e->pend.total = total;
     e->pend.dr = dr;
     e->pend.d_wp = d_wp;
@@ -3349,7 +3361,10 @@ static int32_t compact_finish(HipEngine *e, rrdb_compact_stats *stats)
         /* keep_inputs drops the output at the end of the pass: arena memory */
         e->alloc_base(nr, n_out, kbytes, vbytes, keep_inputs ? RunAlloc::Arena : RunAlloc::Abort);
         HIP_OK(hipEventRecord(ev[3], e->stream));
-        if (e->emit_mode == 2 || e->pend.chunked || e->pend.fk || e->pend.no_rewrite) {
+        /* fk and no_rewrite imply the chunked emit (compact_begin) */
+        if (e->pend.emit_mode == 2) {
+            e->last_route.emit =
+                e->pend.fk ? RRDB_ROUTE_EMIT_CHUNKED_FIXED : RRDB_ROUTE_EMIT_CHUNKED;
             uint64_t *d_row_ksrc = e->talloc<uint64_t>(n_out * 8);
             uint64_t *d_row_vsrc = e->talloc<uint64_t>(n_out * 8);
             uint32_t *d_row_patch = e->talloc<uint32_t>(n_out * 4);
@@ -3364,15 +3379,18 @@ static int32_t compact_finish(HipEngine *e, rrdb_compact_stats *stats)
                                         d_row_expire, nr.keys, nr.vals, nr.koff, nr.voff, nr.sk,
                                         d_kanchor, d_vanchor, e->pend.fk, e->pend.fv,
                                         e->stream);
-        } else if (e->emit_mode == 1)
+        } else if (e->pend.emit_mode == 1) {
+            e->last_route.emit = RRDB_ROUTE_EMIT_INPUT;
             launch_emit_compact_inmajor(dr, R, d_wp, total, d_rank_of, d_keepw, d_changed,
                                         d_new_expire, d_kpos, d_koffs, d_voffs,
                                         e->data_version, nr.keys, nr.vals, nr.koff, nr.voff,
                                         nr.sk, n_out, e->stream);
-        else
+        } else {
+            e->last_route.emit = RRDB_ROUTE_EMIT_RANK;
             launch_emit_compact(dr, d_order, total, d_keepw, d_changed, d_new_expire, d_kpos,
                                 d_koffs, d_voffs, e->data_version, nr.keys, nr.vals, nr.koff,
                                 nr.voff, nr.sk, n_out, e->stream);
+        }
         HIP_OK(hipEventRecord(ev[4], e->stream));
         e->tev_have_emit = true;
         if (!keep_inputs) {
@@ -3449,6 +3467,16 @@ static int32_t compact_window(HipEngine *e, size_t first, size_t n, uint32_t epo
         return rc;
     }
     return compact_finish(e, stats);
+}
+
+int32_t rrdb_last_compact_route(void *h, rrdb_compact_route *out)
+{
+    auto *e = (HipEngine *)h;
+    if (!out)
+        return RRDB_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> g(e->mu);
+    *out = e->last_route;
+    return RRDB_OK;
 }
 
 int32_t rrdb_compact_runs(void *h, uint64_t first_run, uint64_t n_runs, uint32_t epoch_now,

@@ -12,7 +12,8 @@ import pytest
 from incubator_pegasus_amd import data as D
 from incubator_pegasus_amd.capi import (FT_MATCH_ANYWHERE, FT_MATCH_PREFIX,
                                         FT_MATCH_POSTFIX, FT_NO_FILTER, INCOMPLETE,
-                                        NOT_FOUND, OK, SCAN_COMPLETED)
+                                        NOT_FOUND, OK, ROUTE_RANK_GLOBAL, ROUTE_RANK_LDS,
+                                        ROUTE_RANK_LDST, SCAN_COMPLETED)
 
 pytestmark = pytest.mark.gpu
 
@@ -409,6 +410,7 @@ def test_compact_parity_lds_rank(oracle_lib, hip_lib, seed):
         g.ingest_run(skew)
         so = o.manual_compact(now)
         sg = g.manual_compact(now)
+        assert g.last_compact_route()[0] == ROUTE_RANK_LDS
         assert so == sg
         assert _drain(o, now, validate_partition_hash=False) == \
                _drain(g, now, validate_partition_hash=False)
@@ -725,6 +727,7 @@ def test_compact_parity_ldst_rank(oracle_lib, hip_lib, n_keys):
         now = 1000
         so = o.manual_compact(now)
         sg = g.manual_compact(now)
+        assert g.last_compact_route()[0] == ROUTE_RANK_LDST
         assert so == sg
         assert o.num_records() == g.num_records()
         probe_ids = D2.zipfian_ids(300, n_keys, seed=7)
@@ -760,6 +763,7 @@ def test_ldst_fallback_branches(oracle_lib, hip_lib):
             o.ingest_run(recs)
             g.ingest_run(recs)
         assert o.manual_compact(now) == g.manual_compact(now)
+        assert g.last_compact_route()[0] == ROUTE_RANK_LDST  # the fallback is in the kernel
         assert _drain(o, now, validate_partition_hash=False) == \
                _drain(g, now, validate_partition_hash=False)
     finally:
@@ -784,6 +788,7 @@ def test_ldst_fallback_branches(oracle_lib, hip_lib):
                 k = D.generate_key(pfx + b"%04d" % i, b"")
                 assert o.get(k, now) == g.get(k, now), k
         assert o.manual_compact(now) == g.manual_compact(now)
+        assert g.last_compact_route()[0] == ROUTE_RANK_GLOBAL
         assert _drain(o, now, validate_partition_hash=False) == \
                _drain(g, now, validate_partition_hash=False)
     finally:

@@ -18,7 +18,7 @@ import numpy as np
 import pytest
 
 from incubator_pegasus_amd import data as D
-from incubator_pegasus_amd.capi import OK, SCAN_COMPLETED
+from incubator_pegasus_amd.capi import OK, ROUTE_RANK_GLOBAL, ROUTE_RANK_GRP, SCAN_COMPLETED
 
 pytestmark = pytest.mark.gpu
 
@@ -56,6 +56,7 @@ def test_compact_parity_grp_rank(oracle_lib, hip_lib, n_keys):
         _ingest_arrays((o, g), runs)
         so = o.manual_compact(NOW)
         sg = g.manual_compact(NOW)
+        assert g.last_compact_route()[0] == ROUTE_RANK_GRP
         assert so == sg
         assert o.num_records() == g.num_records()
         for k in [bytes(x) for x in D.make_raw_keys(D.zipfian_ids(300, n_keys, seed=7))]:
@@ -87,6 +88,7 @@ def test_grp_rank_identical_runs_boundary_splits(oracle_lib, hip_lib):
             g.ingest_run(recs)
         so = o.manual_compact(NOW)
         sg = g.manual_compact(NOW)
+        assert g.last_compact_route()[0] == ROUTE_RANK_GRP
         assert so == sg
         assert so[1].shadowed == 4 * 3000
         assert _drain(o, NOW, validate_partition_hash=False) == \
@@ -99,19 +101,22 @@ def test_grp_rank_identical_runs_boundary_splits(oracle_lib, hip_lib):
 def test_grp_rank_oversized_group_fallback(oracle_lib, hip_lib):
     """Run 1's keys all cluster between two anchor keys of run 0 (the anchor
     run): one group far exceeds GRP_CAP and takes the in-kernel global-probe
-    fallback; the rest stay staged."""
+    fallback; the rest stay staged.  The ids stay below 10^8, so every key
+    shares the 10 bytes before its tail word and the runs are eligible for
+    the group rank at all (ids spaced 10^6 apart were not: the pass went to
+    the global kernel and never met an oversized group)."""
     o = oracle_lib.open(1, 0, -1)
     g = hip_lib.open(1, 0, 0)
     try:
         g.set_envs({"engine.rank_mode": "grp"})
-        # run 0 (anchor: largest): 10000 keys spaced 1e6 apart
-        ids0 = np.arange(10000, dtype=np.uint64) * np.uint64(1000000)
+        # run 0 (anchor: largest): 10000 keys spaced 1e4 apart
+        ids0 = np.arange(10000, dtype=np.uint64) * np.uint64(10000)
         keys0 = D.make_raw_keys(ids0)
         recs0 = [(bytes(keys0[j]), D.encode_value(b"a%d" % j, 0, j + 1, 1), j + 1, 0)
                  for j in range(len(ids0))]
         # run 1: 5000 keys ALL between two consecutive run-0 keys -> one
         # group of ~5000+stride records, far over GRP_CAP
-        ids1 = np.uint64(500000) + np.arange(5000, dtype=np.uint64)
+        ids1 = np.uint64(2500) + np.arange(5000, dtype=np.uint64)
         keys1 = D.make_raw_keys(ids1)
         s0 = len(ids0) + 1
         recs1 = [(bytes(keys1[j]), D.encode_value(b"b%d" % j, 0, s0 + j, 1), s0 + j, 0)
@@ -121,6 +126,7 @@ def test_grp_rank_oversized_group_fallback(oracle_lib, hip_lib):
             part.ingest_run(recs1)
         so = o.manual_compact(NOW)
         sg = g.manual_compact(NOW)
+        assert g.last_compact_route()[0] == ROUTE_RANK_GRP
         assert so == sg
         assert so[1].output_records == len(ids0) + len(ids1)
         assert _drain(o, NOW, validate_partition_hash=False) == \
@@ -150,6 +156,7 @@ def test_grp_rank_many_runs_uses_fallback_mode(oracle_lib, hip_lib):
             o.ingest_run(recs)
             g.ingest_run(recs)
         assert o.manual_compact(NOW) == g.manual_compact(NOW)
+        assert g.last_compact_route()[0] == ROUTE_RANK_GLOBAL
         assert _drain(o, NOW, validate_partition_hash=False) == \
                _drain(g, NOW, validate_partition_hash=False)
     finally:
@@ -379,6 +386,7 @@ def test_grp_rank_rules_and_ttl(oracle_lib, hip_lib):
         _ingest_arrays((o, g), runs)
         so = o.manual_compact(NOW)
         sg = g.manual_compact(NOW)
+        assert g.last_compact_route()[0] == ROUTE_RANK_GRP
         assert so == sg
         assert so[1].filtered > 0
         assert _drain(o, NOW, validate_partition_hash=False) == \

@@ -15,7 +15,8 @@ import random
 import pytest
 
 from incubator_pegasus_amd import data as D
-from incubator_pegasus_amd.capi import INVALID_ARGUMENT, NOT_FOUND, OK, SCAN_COMPLETED
+from incubator_pegasus_amd.capi import (INVALID_ARGUMENT, NOT_FOUND, OK, ROUTE_EMIT_CHUNKED,
+                                        ROUTE_RANK_GLOBAL, ROUTE_RANK_GRP, SCAN_COMPLETED)
 from pymodel import Model, crc64
 from test_minor_compact_model import (NOW, apply_window, build_model, delete_rule_env, drain,
                                       fixed_key, hash_keys_of, ingest_model, merge_window,
@@ -135,6 +136,9 @@ def test_upper_window(hip_lib, oracle_lib, schema):
                for k, (_, _, kd) in newest_in_win.items())  # tombstone over a live PUT
     g, b, st = _window_case(hip_lib, oracle_lib, m, 1, 2)
     try:
+        # the kernels SCHEMAS names; a window pass always emits chunked
+        assert g.last_compact_route() == (
+            ROUTE_RANK_GRP if schema == "fixed" else ROUTE_RANK_GLOBAL, ROUTE_EMIT_CHUNKED)
         assert st["tombstones"] == 0 and st["expired"] > 0 and st["shadowed"] > 0
         assert st["input_records"] == st["output_records"] + st["shadowed"]
         assert g.num_runs() == 3
@@ -274,6 +278,7 @@ def test_upper_window_global_rank_mode(hip_lib, oracle_lib):
         want = apply_window(m, 1, 3, NOW)
         err, got = g.compact_runs(1, 3, NOW)
         assert err == OK and stats_dict(got) == want
+        assert g.last_compact_route() == (ROUTE_RANK_GLOBAL, ROUTE_EMIT_CHUNKED)
         ingest_model(b, m)
         _same_reads(g, b, keys[::3], hks)
         _same_full_compact(g, b)

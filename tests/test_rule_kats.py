@@ -3,50 +3,17 @@
     (hashkey/sortkey pattern matrices, ttl_range matrix)
   - src/server/test/compaction_operation_test.cpp:250-287 (ops JSON format)
 Exercised through the oracle's pattern hook AND end-to-end through
-rrdb_set_envs("user_specified_compaction") + rrdb_manual_compact."""
+rrdb_set_envs("user_specified_compaction") + rrdb_manual_compact.  The tables
+and builders live in tests/rule_tables.py, shared with the device run of the
+same rows (tests/test_rule_tables_gpu.py)."""
 import ctypes
 import json
 
 from conftest import ORACLE_SO
-from incubator_pegasus_amd import data as D
-
-SMT_ANYWHERE, SMT_PREFIX, SMT_POSTFIX, SMT_INVALID = 0, 1, 2, 3
-
-# compaction_filter_rule_test.cpp:40-57 (hashkey table; sortkey table is the
-# same matrix over the sortkey, :75-92)
-PATTERN_CASES = [
-    (b"sortkey", b"", SMT_ANYWHERE, False),
-    (b"hashkey", b"hashkey", SMT_ANYWHERE, True),
-    (b"hashkey", b"shke", SMT_ANYWHERE, True),
-    (b"hashkey", b"hash", SMT_ANYWHERE, True),
-    (b"hashkey", b"key", SMT_ANYWHERE, True),
-    (b"hashkey", b"sortkey", SMT_ANYWHERE, False),
-    (b"hashkey", b"hashkey", SMT_PREFIX, True),
-    (b"hashkey", b"hash", SMT_PREFIX, True),
-    (b"hashkey", b"key", SMT_PREFIX, False),
-    (b"hashkey", b"sortkey", SMT_PREFIX, False),
-    (b"hashkey", b"hashkey", SMT_POSTFIX, True),
-    (b"hashkey", b"hash", SMT_POSTFIX, False),
-    (b"hashkey", b"key", SMT_POSTFIX, True),
-    (b"hashkey", b"sortkey", SMT_POSTFIX, False),
-    (b"hash", b"hashkey", SMT_POSTFIX, False),
-    (b"hashkey", b"hashkey", SMT_INVALID, False),
-]
-
-# compaction_filter_rule_test.cpp:105-125: (start_ttl, stop_ttl, expire_ttl, match)
-TTL_RANGE_CASES = [
-    (100, 1000, 1100, False),
-    (100, 1000, 500, True),
-    (100, 1000, 20, False),
-    (100, 1000, 0, False),
-    (1000, 100, 1100, False),
-    (1000, 100, 500, False),
-    (1000, 100, 20, False),
-    (1000, 100, 0, False),
-    (0, 1000, 500, True),
-    (1000, 0, 500, False),
-    (0, 0, 0, True),
-]
+from rule_tables import PATTERN_CASES, TTL_RANGE_CASES
+from rule_tables import mk_rule as _mk_rule
+from rule_tables import one_key_compact as _one_key_compact
+from rule_tables import ops_json as _ops_json
 
 
 def test_pattern_match_table():
@@ -57,41 +24,6 @@ def test_pattern_match_table():
     for value, pat, mt, want in PATTERN_CASES:
         got = lib.orc_pattern_match(value, len(value), mt, pat, len(pat))
         assert bool(got) == want, (value, pat, mt)
-
-
-def _mk_rule(rtype, params):
-    return {"type": rtype, "params": json.dumps(params)}
-
-
-def _ops_json(ops):
-    return json.dumps({"ops": [
-        {"type": t, "params": json.dumps(p) if isinstance(p, dict) else p,
-         "rules": rules} for t, p, rules in ops]})
-
-
-def _one_key_compact(oracle_lib, ops_json, value_expire, now, hash_key=b"hashkey",
-                     sort_key=b"sortkey", envs=None):
-    """Ingest a single record and compact; returns (survived, new_expire_ts)."""
-    p = oracle_lib.open(1, 0, -1)
-    try:
-        if envs:
-            p.set_envs(envs)
-        if ops_json is not None:
-            p.set_envs({"user_specified_compaction": ops_json})
-        raw_key = D.generate_key(hash_key, sort_key)
-        val = D.encode_value(b"payload", value_expire, 0, 1)
-        p.ingest_run([(raw_key, val, 10, 0)])
-        err, stats = p.manual_compact(now)
-        assert err == 0
-        if stats.output_records == 0:
-            return False, None
-        st, got = p.get(raw_key, 0)  # epoch 0: nothing TTL-hidden at read time
-        assert st == 0
-        st, ttl = p.ttl(raw_key, 0)
-        # recover expire via ttl(+0): ttl == expire - 0 when expire>0 else -1
-        return True, (None if ttl == -1 else ttl)
-    finally:
-        p.close()
 
 
 def test_ttl_range_rule_matrix(oracle_lib):

@@ -1,0 +1,648 @@
+"""The compaction-filter decision tables on the device, per dispatch route.
+
+The engine has its own ops-JSON parser (parse_user_ops), flattening
+(upload_ops) and evaluator (dev_filter_disposition / dev_pattern_match); four
+rank kernels call the evaluator and four emit forms apply its header rewrites.
+Three layers, all exact (integers and bytes, no tolerance):
+
+  2a  the reference's literal rows (tests/rule_tables.py), one record each,
+      against the engine and the oracle, plus the parser's edge rows;
+  2b  every rule set of rule_tables.rule_sets on small 3-run layouts, for
+      every (engine.rank_mode, engine.emit_mode), asserting the route that
+      rrdb_last_compact_route reports, the full stats and a full drain with
+      expire headers against the oracle and tests/pymodel.py; the rewriting
+      sets again under data versions 0 and 2; one window pass;
+  2c  (no GPU) the oracle against pymodel on the same rule sets, and a
+      self-check that no rule set passes vacuously.
+"""
+import ctypes
+import json
+import os
+import re
+
+import pytest
+
+from conftest import HIP_SO, REPO
+from incubator_pegasus_amd import data as D
+from incubator_pegasus_amd.capi import (NOT_FOUND, OK, ROUTE_EMIT_CHUNKED,
+                                        ROUTE_EMIT_CHUNKED_FIXED, ROUTE_EMIT_INPUT,
+                                        ROUTE_EMIT_RANK, ROUTE_NONE, ROUTE_RANK_GLOBAL,
+                                        ROUTE_RANK_GRP, ROUTE_RANK_LDS, ROUTE_RANK_LDST)
+from pymodel import Model, expire_of
+from rule_tables import (EPOCH_BEGIN, LAYOUTS, NOW, PATTERN_CASES, REWRITING, SMT_ANYWHERE,
+                         SMT_NAMES, SMT_PREFIX, TTL_HI, TTL_LO, TTL_RANGE_CASES, RuleSet,
+                         build_runs, make_model, mk_rule, model_ops, model_rows,
+                         one_key_compact, open_part, ops_json, pattern_rule, rule_sets,
+                         set_rule_envs, ttl_rule)
+from test_minor_compact_model import (apply_window, drain, ingest_model, merge_window,
+                                      stats_dict)
+
+gpu = pytest.mark.gpu
+
+HASH_PREFIX = [mk_rule("FRT_HASHKEY_PATTERN",
+                       {"pattern": "hash", "match_type": "SMT_MATCH_PREFIX"})]
+
+
+@pytest.fixture()
+def both(oracle_lib, hip_lib):
+    """the rows are asserted on the engine and, equally, on the oracle"""
+    return (oracle_lib, hip_lib)
+
+
+def _one(libs, want, *args, **kw):
+    for lib in libs:
+        assert one_key_compact(lib, *args, **kw) == want, (lib.backend, args, kw)
+
+
+# ======================= 2a: one record per row =======================
+
+@gpu
+def test_ttl_range_rule_matrix(both):
+    """ttl_range_rule::match (compaction_filter_rule.cpp:74-90) through a
+    delete op: record dropped iff the rule matches."""
+    now = 1000000
+    for start_ttl, stop_ttl, expire_ttl, want_match in TTL_RANGE_CASES:
+        ops = ops_json([("COT_DELETE", "", [ttl_rule(start_ttl, stop_ttl)])])
+        expire = (expire_ttl + now) if expire_ttl else 0
+        for lib in both:
+            survived, _ = one_key_compact(lib, ops, expire, now)
+            assert survived == (not want_match), (lib.backend, start_ttl, stop_ttl, expire_ttl)
+
+
+@gpu
+@pytest.mark.parametrize("part", ["hashkey", "sortkey"])
+def test_pattern_rows_through_delete(both, part):
+    """The 16 pattern rows (string_pattern_match, compaction_filter_rule.cpp:
+    31-53) through a COT_DELETE op with one rule on `part`: dropped iff the
+    table says match.  The other key part holds the row's value reversed, so
+    a rule that looks at the wrong part decides wrongly."""
+    for value, pat, mt, want in PATTERN_CASES:
+        ops = ops_json([("COT_DELETE", "", [pattern_rule(part, pat, mt)])])
+        other = value[::-1] + b"#"
+        hk, sk = (value, other) if part == "hashkey" else (other, value)
+        for lib in both:
+            survived, _ = one_key_compact(lib, ops, 0, 100, hash_key=hk, sort_key=sk)
+            assert survived == (not want), (lib.backend, part, value, pat, SMT_NAMES[mt])
+
+
+@gpu
+def test_delete_op_pattern_rules(both):
+    """delete_key::filter (compaction_operation.cpp:57-68): drops iff ALL rules match."""
+    ops = ops_json([("COT_DELETE", "", [
+        mk_rule("FRT_HASHKEY_PATTERN", {"pattern": "hash", "match_type": "SMT_MATCH_PREFIX"}),
+        mk_rule("FRT_SORTKEY_PATTERN", {"pattern": "key", "match_type": "SMT_MATCH_POSTFIX"}),
+    ])])
+    _one(both, (False, None), ops, 0, 100)  # both match -> dropped
+    ops2 = ops_json([("COT_DELETE", "", [
+        mk_rule("FRT_HASHKEY_PATTERN", {"pattern": "hash", "match_type": "SMT_MATCH_PREFIX"}),
+        mk_rule("FRT_SORTKEY_PATTERN", {"pattern": "nope", "match_type": "SMT_MATCH_POSTFIX"}),
+    ])])
+    _one(both, (True, None), ops2, 0, 100)  # second rule fails -> kept
+
+
+@gpu
+def test_update_ttl_ops(both):
+    """update_ttl::filter (compaction_operation.cpp:78-113)."""
+    now = 500000
+    # UTOT_FROM_NOW: new expire = now + value
+    ops = ops_json([("COT_UPDATE_TTL", {"type": "UTOT_FROM_NOW", "value": 1234}, HASH_PREFIX)])
+    _one(both, (True, now + 1234), ops, 0, now)
+    # UTOT_FROM_CURRENT on a no-ttl record: no-op
+    ops = ops_json([("COT_UPDATE_TTL", {"type": "UTOT_FROM_CURRENT", "value": 100}, HASH_PREFIX)])
+    _one(both, (True, None), ops, 0, now)
+    # UTOT_FROM_CURRENT with existing ttl
+    _one(both, (True, now + 150), ops, now + 50, now)
+    # UTOT_TIMESTAMP: expire = value - epoch_begin(1451606400)
+    ops = ops_json([("COT_UPDATE_TTL", {"type": "UTOT_TIMESTAMP", "value": EPOCH_BEGIN + 777777},
+                     HASH_PREFIX)])
+    _one(both, (True, 777777), ops, 0, now)
+
+
+@gpu
+def test_default_ttl_rewrite(both):
+    """Filter:73-79: default_ttl applied to expire_ts==0 records during compaction."""
+    now = 300000
+    _one(both, (True, now + 5000), None, 0, now, envs={"default_ttl": "5000"})
+    # record with own ttl is untouched
+    _one(both, (True, now + 99), None, now + 99, now, envs={"default_ttl": "5000"})
+
+
+@gpu
+def test_invalid_ops_json_means_no_ops(both):
+    """create_compaction_operations: bad json -> empty ops (cpp:165-169);
+    ops with zero valid rules are skipped (:176-179)."""
+    now = 1000
+    _one(both, (True, None), "not json at all", 0, now)
+    # delete op with only an invalid-typed rule: skipped -> survives
+    ops = json.dumps({"ops": [{"type": "COT_DELETE", "params": "",
+                               "rules": [{"type": "FRT_BOGUS", "params": "{}"}]}]})
+    _one(both, (True, None), ops, 0, now)
+    # rule params missing a required field -> rule invalid -> op skipped
+    ops = json.dumps({"ops": [{"type": "COT_DELETE", "params": "", "rules": [
+        {"type": "FRT_HASHKEY_PATTERN",
+         "params": json.dumps({"pattern_xxx": "h", "match_type": "SMT_MATCH_PREFIX"})}]}]})
+    _one(both, (True, None), ops, 0, now)
+
+
+@gpu
+def test_op_order_first_delete_wins(both):
+    """ops applied in order; a matching delete drops immediately
+    (key_ttl_compaction_filter.h:101-107)."""
+    ops = ops_json([
+        ("COT_DELETE", "", HASH_PREFIX),
+        ("COT_UPDATE_TTL", {"type": "UTOT_FROM_NOW", "value": 55}, HASH_PREFIX),
+    ])
+    _one(both, (False, None), ops, 0, 100)
+
+
+# Parser rows.  The rule each one restates is the comment on parse_user_ops
+# (engine.cpp) and on parse_user_ops / parse_op_params (oracle): a missing
+# "params" decodes as "" (json_helper.h JSON_TRY_DECODE_ENTRY tolerates absent
+# members), which delete_key ignores and update_ttl fails to decode; invalid
+# rules are skipped and the op lives on the valid ones
+# (create_compaction_filter_rules, compaction_operation.cpp:148-160); an
+# update_ttl with an unknown type is created and never applies (:104-106).
+# want = (survived, expire); the record is hashkey/sortkey with no TTL.
+_FROM_NOW_9 = json.dumps({"type": "UTOT_FROM_NOW", "value": 9})
+_NOMATCH = [mk_rule("FRT_HASHKEY_PATTERN", {"pattern": "nope", "match_type": "SMT_MATCH_PREFIX"})]
+_BOGUS = {"type": "FRT_BOGUS", "params": "{}"}
+PARSER_ROWS = [
+    ("delete_without_params_kept",
+     {"ops": [{"type": "COT_DELETE", "rules": HASH_PREFIX}]}, (False, None)),
+    ("delete_without_params_still_needs_a_match",
+     {"ops": [{"type": "COT_DELETE", "rules": _NOMATCH}]}, (True, None)),
+    ("update_ttl_without_params_dropped",
+     {"ops": [{"type": "COT_UPDATE_TTL", "rules": HASH_PREFIX}]}, (True, None)),
+    ("update_ttl_params_lack_value_dropped",
+     {"ops": [{"type": "COT_UPDATE_TTL", "params": json.dumps({"type": "UTOT_FROM_NOW"}),
+               "rules": HASH_PREFIX}]}, (True, None)),
+    ("update_ttl_params_lack_type_dropped",
+     {"ops": [{"type": "COT_UPDATE_TTL", "params": json.dumps({"value": 9}),
+               "rules": HASH_PREFIX}]}, (True, None)),
+    ("dropped_op_does_not_stop_the_next",
+     {"ops": [{"type": "COT_UPDATE_TTL", "params": json.dumps({"type": "UTOT_FROM_NOW"}),
+               "rules": HASH_PREFIX},
+              {"type": "COT_UPDATE_TTL", "params": _FROM_NOW_9, "rules": HASH_PREFIX}]},
+     (True, 1000 + 9)),
+    ("bogus_rule_skipped_op_kept_on_valid_rule",
+     {"ops": [{"type": "COT_DELETE", "params": "", "rules": [_BOGUS] + HASH_PREFIX}]},
+     (False, None)),
+    ("bogus_rule_skipped_valid_rule_still_decides",
+     {"ops": [{"type": "COT_DELETE", "params": "", "rules": HASH_PREFIX + [_BOGUS] + _NOMATCH}]},
+     (True, None)),
+    ("ops_not_an_array_object",
+     {"ops": {"type": "COT_DELETE", "params": "", "rules": HASH_PREFIX}}, (True, None)),
+    ("ops_not_an_array_number", {"ops": 7}, (True, None)),
+    ("ops_member_absent", {"sop": []}, (True, None)),
+    ("unknown_extra_members",
+     {"version": 2, "note": {"a": [1, 2, {"b": None}], "c": True},
+      "ops": [{"comment": "x", "type": "COT_DELETE", "priority": -3, "params": "",
+               "rules": [{"id": [False], "type": "FRT_HASHKEY_PATTERN",
+                          "params": json.dumps({"pattern": "hash", "case": None,
+                                                "match_type": "SMT_MATCH_PREFIX"})}]}]},
+     (False, None)),
+    ("unknown_utot_type_never_applies",
+     {"ops": [{"type": "COT_UPDATE_TTL", "params": json.dumps({"type": "UTOT_BOGUS", "value": 9}),
+               "rules": HASH_PREFIX}]}, (True, None)),
+    ("unknown_utot_type_then_valid_op",
+     {"ops": [{"type": "COT_UPDATE_TTL", "params": json.dumps({"type": "UTOT_BOGUS", "value": 5}),
+               "rules": HASH_PREFIX},
+              {"type": "COT_UPDATE_TTL", "params": _FROM_NOW_9, "rules": HASH_PREFIX}]},
+     (True, 1000 + 9)),
+    ("unknown_op_type_skipped",
+     {"ops": [{"type": "COT_BOGUS", "params": "", "rules": HASH_PREFIX},
+              {"type": "COT_UPDATE_TTL", "params": _FROM_NOW_9, "rules": HASH_PREFIX}]},
+     (True, 1000 + 9)),
+]
+
+
+@gpu
+@pytest.mark.parametrize("name,doc,want", PARSER_ROWS, ids=[r[0] for r in PARSER_ROWS])
+def test_parser_rows(both, name, doc, want):
+    text = json.dumps(doc)
+    _one(both, want, text, 0, 1000)
+    # and model_ops, which feeds pymodel in the matrix below, reads it alike
+    m = Model()
+    key = D.generate_key(b"hashkey", b"sortkey")
+    m.ingest([(key, D.encode_value(b"payload", 0, 0, 1), 10, 0)])
+    m.user_ops = model_ops(text)
+    surviving, _ = m.compact_full(1000)
+    got = (True, expire_of(surviving[key][0], 1) or None) if surviving else (False, None)
+    assert got == want
+
+
+@gpu
+def test_parser_escapes_in_pattern(both):
+    """A pattern with an escaped quote, an escaped backslash and a \\u00XX
+    escape.  The rule params are a JSON text inside a JSON string, so the
+    outer parser unescapes \\" and \\\\ and the inner one \\u00e9."""
+    hk = b'ha"s\\h\xe9key'
+    hit = pattern_rule("hashkey", b'a"s\\h\xe9k', SMT_ANYWHERE)
+    assert "\\\\u00e9" in json.dumps(hit) and '\\\\\\"' in json.dumps(hit)
+    miss = pattern_rule("hashkey", b'a"s\\h\xe8k', SMT_ANYWHERE)
+    _one(both, (False, None), ops_json([("COT_DELETE", "", [hit])]), 0, 1000, hash_key=hk)
+    _one(both, (True, None), ops_json([("COT_DELETE", "", [miss])]), 0, 1000, hash_key=hk)
+    # the escape at the outer level: "type" is the member name "type"
+    text = ops_json([("COT_DELETE", "", [hit])]).replace('"type": "COT', '"\\u0074ype": "COT')
+    assert "\\u0074ype" in text
+    _one(both, (False, None), text, 0, 1000, hash_key=hk)
+
+
+@gpu
+def test_one_record_route(hip_lib):
+    """R = 1, total = 1: the global rank kernel; one key stride and one value
+    stride, so the chunked emit runs in its all-fixed-stride form.  A pass
+    that emits nothing reports no emit, an empty handle no rank either."""
+    g = open_part(hip_lib)
+    try:
+        assert g.last_compact_route() == (ROUTE_NONE, ROUTE_NONE)
+        assert g.manual_compact(100)[0] == OK
+        assert g.last_compact_route() == (ROUTE_NONE, ROUTE_NONE)
+        g.ingest_run([(D.generate_key(b"hashkey", b"sortkey"),
+                       D.encode_value(b"payload", 0, 0, 1), 10, 0)])
+        assert g.manual_compact(100)[0] == OK
+        assert g.last_compact_route() == (ROUTE_RANK_GLOBAL, ROUTE_EMIT_CHUNKED_FIXED)
+        g.set_envs({"user_specified_compaction": ops_json([("COT_DELETE", "", HASH_PREFIX)])})
+        err, st = g.manual_compact(100)
+        assert err == OK and st.output_records == 0 and st.filtered == 1
+        assert g.last_compact_route() == (ROUTE_RANK_GLOBAL, ROUTE_NONE)
+        assert g.manual_compact(100)[0] == OK  # nothing left: trivial pass
+        assert g.last_compact_route() == (ROUTE_NONE, ROUTE_NONE)
+    finally:
+        g.close()
+
+
+@gpu
+@pytest.mark.parametrize("version", [1, 0, 2])
+@pytest.mark.parametrize("emit_mode,emit", [("rank", ROUTE_EMIT_RANK),
+                                            ("input", ROUTE_EMIT_INPUT)])
+def test_one_record_wave_emits(both, emit_mode, emit, version):
+    """k_emit_compact and k_emit_compact_inmajor at their smallest: one record
+    whose header they patch themselves, at the offset of each data version."""
+    now = 300000
+    key = D.generate_key(b"hashkey", b"sortkey")
+    ops = ops_json([("COT_UPDATE_TTL", {"type": "UTOT_FROM_CURRENT", "value": 100}, HASH_PREFIX)])
+    for lib in both:
+        # default_ttl makes 0 -> now + 5000, and FROM_CURRENT sees that
+        for expire, want in ((0, now + 5100), (now + 99, now + 199)):
+            p = open_part(lib)
+            try:
+                p.set_envs({"pegasus.data_version": str(version), "default_ttl": "5000",
+                            "user_specified_compaction": ops, "engine.emit_mode": emit_mode})
+                p.ingest_run([(key, D.encode_value(b"payload", expire, 7, version), 10, 0)])
+                err, st = p.manual_compact(now)
+                assert err == OK and st.output_records == 1
+                if lib is not both[0]:
+                    assert p.last_compact_route() == (ROUTE_RANK_GLOBAL, emit)
+                assert drain(p, 0) == [(key, b"payload", want)], (lib.backend, expire)
+            finally:
+                p.close()
+
+
+# ======================= 2b: rule sets x routes =======================
+
+_REF = {}
+
+
+def reference(oracle_lib, layout, rs, version=1):
+    """(stats dict, drain rows at epoch 0) of the full compaction of `layout`
+    under `rs`, computed once: Model.compact_full and the oracle, which must
+    agree before anything is compared with them."""
+    key = (layout, rs.name, version)
+    if key not in _REF:
+        surviving, mstats = make_model(layout, rs, version).compact_full(NOW)
+        o = open_part(oracle_lib)
+        try:
+            set_rule_envs(o, rs, version)
+            for run in build_runs(layout, version):
+                o.ingest_run(run)
+            err, so = o.manual_compact(NOW)
+            assert err == OK
+            rows = drain(o, 0)
+        finally:
+            o.close()
+        assert stats_dict(so) == mstats, key
+        assert rows == model_rows(surviving, version), key
+        _REF[key] = (mstats, rows)
+    return _REF[key]
+
+
+G, L, T, P = ROUTE_RANK_GLOBAL, ROUTE_RANK_LDS, ROUTE_RANK_LDST, ROUTE_RANK_GRP
+RK, IN, CH, FX = (ROUTE_EMIT_RANK, ROUTE_EMIT_INPUT, ROUTE_EMIT_CHUNKED,
+                  ROUTE_EMIT_CHUNKED_FIXED)
+# (engine.rank_mode, engine.emit_mode, layout) -> (rank, emit), from a reading
+# of compact_begin / compact_finish for a manual pass over 3 runs that emits
+# at least one record:
+#   rank  lds   iff rank_mode == lds and emit_mode == chunked (R > 1);
+#         grp   else iff rank_mode == grp, emit_mode != input, R <= 32 and the
+#               runs are tail-word eligible (word, wordvar);
+#         ldst  else iff rank_mode == ldst and the runs are eligible;
+#         global otherwise: lds with a wave emit, grp with the input-major
+#               emit, and either tail-word mode on the variable layout.  (ldst
+#               is never a fallback: ldst_eligible requires rank_mode == ldst.)
+#   emit  rank / input as asked; chunked becomes its all-fixed-stride form
+#         iff the pass is bottommost and the runs share one key stride and one
+#         PUT-value stride (word; not wordvar, not var).
+ROUTE_TABLE = [
+    ("global", "chunked", "var", (G, CH)),
+    ("global", "chunked", "word", (G, FX)),
+    ("global", "rank", "var", (G, RK)),
+    ("global", "input", "var", (G, IN)),
+    ("lds", "chunked", "var", (L, CH)),
+    ("lds", "chunked", "word", (L, FX)),
+    ("lds", "rank", "var", (G, RK)),
+    ("lds", "input", "word", (G, IN)),
+    ("ldst", "chunked", "wordvar", (T, CH)),
+    ("ldst", "chunked", "word", (T, FX)),
+    ("ldst", "rank", "word", (T, RK)),
+    ("ldst", "input", "word", (T, IN)),
+    ("ldst", "chunked", "var", (G, CH)),
+    ("grp", "chunked", "wordvar", (P, CH)),
+    ("grp", "chunked", "word", (P, FX)),
+    ("grp", "rank", "word", (P, RK)),
+    ("grp", "input", "word", (G, IN)),
+    ("grp", "rank", "var", (G, RK)),
+]
+_RANK_NAME = {G: "global", L: "lds", T: "ldst", P: "grp"}
+_EMIT_NAME = {RK: "rank-major", IN: "input-major", CH: "chunked", FX: "fixed-chunked"}
+
+
+def _route_id(row):
+    rank_mode, emit_mode, layout, (rank, emit) = row
+    return "%s-%s-%s=%sx%s" % (rank_mode, emit_mode, layout, _RANK_NAME[rank], _EMIT_NAME[emit])
+
+
+def test_route_table_reaches_every_pair():
+    """every (rank, emit) pair the dispatch can produce is asked for"""
+    reachable = ({(G, e) for e in (CH, FX, RK, IN)} | {(L, CH), (L, FX)} |
+                 {(T, e) for e in (CH, FX, RK, IN)} | {(P, CH), (P, FX), (P, RK)})
+    assert {row[3] for row in ROUTE_TABLE} == reachable
+    modes = {(row[0], row[1]) for row in ROUTE_TABLE}
+    assert modes == {(r, e) for r in ("global", "lds", "ldst", "grp")
+                     for e in ("chunked", "rank", "input")}
+
+
+def _engine_pass(hip_lib, layout, rs, rank_mode, emit_mode, version=1):
+    g = open_part(hip_lib)
+    try:
+        g.set_envs({"engine.rank_mode": rank_mode, "engine.emit_mode": emit_mode})
+        set_rule_envs(g, rs, version)
+        for run in build_runs(layout, version):
+            g.ingest_run(run)
+        err, sg = g.manual_compact(NOW)
+        assert err == OK
+        return g.last_compact_route(), stats_dict(sg), drain(g, 0)
+    finally:
+        g.close()
+
+
+@gpu
+@pytest.mark.parametrize("rank_mode,emit_mode,layout,want", ROUTE_TABLE,
+                         ids=[_route_id(r) for r in ROUTE_TABLE])
+def test_rule_sets_on_route(oracle_lib, hip_lib, rank_mode, emit_mode, layout, want):
+    for rs in rule_sets(layout):
+        mstats, rows = reference(oracle_lib, layout, rs)
+        route, stats, got = _engine_pass(hip_lib, layout, rs, rank_mode, emit_mode)
+        assert route == want, rs.name
+        assert stats == mstats, rs.name
+        assert got == rows, rs.name
+
+
+@gpu
+@pytest.mark.parametrize("begun,later,emit", [("rank", "input", RK), ("chunked", "input", CH),
+                                              ("input", "chunked", IN)])
+def test_finish_emits_what_begin_prepared(oracle_lib, hip_lib, begun, later, emit):
+    """The split pass: rrdb_manual_compact_begin builds the arrays of one emit
+    kernel (rank_of only for input-major, row sizes only without the
+    all-fixed-stride form).  An engine.emit_mode set between begin and finish
+    applies to the next pass, not to the pending one."""
+    rs = next(r for r in rule_sets("var") if r.name == "from_current_default_ttl")
+    mstats, rows = reference(oracle_lib, "var", rs)
+    g = open_part(hip_lib)
+    try:
+        g.set_envs({"engine.rank_mode": "global", "engine.emit_mode": begun})
+        set_rule_envs(g, rs)
+        for run in build_runs("var"):
+            g.ingest_run(run)
+        assert g.manual_compact_begin(NOW) == OK
+        assert g.last_compact_route() == (G, ROUTE_NONE)
+        g.set_envs({"engine.emit_mode": later})
+        err, sg = g.manual_compact_finish()
+        assert err == OK
+        assert g.last_compact_route() == (G, emit)
+        assert stats_dict(sg) == mstats
+        assert drain(g, 0) == rows
+    finally:
+        g.close()
+
+
+# one route per emit kernel: header offset 0 (version 0) against 1 (version 2)
+VERSION_ROUTES = [r for r in ROUTE_TABLE if r[:3] in (("global", "chunked", "var"),
+                                                      ("grp", "chunked", "word"),
+                                                      ("grp", "rank", "word"),
+                                                      ("ldst", "input", "word"))]
+
+
+@gpu
+@pytest.mark.parametrize("version", [0, 2])
+@pytest.mark.parametrize("rank_mode,emit_mode,layout,want", VERSION_ROUTES,
+                         ids=[_route_id(r) for r in VERSION_ROUTES])
+def test_rewriting_sets_per_data_version(oracle_lib, hip_lib, rank_mode, emit_mode, layout,
+                                         want, version):
+    assert len(VERSION_ROUTES) == 4 and {r[3][1] for r in VERSION_ROUTES} == {CH, FX, RK, IN}
+    for rs in rule_sets(layout):
+        if not rs.rewrite:
+            continue
+        mstats, rows = reference(oracle_lib, layout, rs, version)
+        route, stats, got = _engine_pass(hip_lib, layout, rs, rank_mode, emit_mode, version)
+        assert route == want, rs.name
+        assert stats == mstats, rs.name
+        assert got == rows, rs.name
+
+
+def _window_rule_set(layout):
+    v = LAYOUTS[layout].vocab
+    ops = ops_json([
+        ("COT_DELETE", "", [pattern_rule("hashkey", v.prefix[0], SMT_PREFIX)]),
+        ("COT_DELETE", "", [ttl_rule(TTL_LO, TTL_HI)]),
+        ("COT_UPDATE_TTL", {"type": "UTOT_FROM_CURRENT", "value": 77},
+         [pattern_rule("sortkey", v.prefix[1], SMT_PREFIX)]),
+    ])
+    return RuleSet("window", ops, 0, False, True)
+
+
+@gpu
+@pytest.mark.parametrize("rank_mode,rank", [("grp", P), ("ldst", T), ("lds", L), ("global", G)])
+def test_window_pass_rules(oracle_lib, hip_lib, rank_mode, rank):
+    """compact_runs(1, 2) over an older run: a window pass always emits
+    chunked, and never all-fixed-stride (converted tombstones have no value);
+    runs 1 and 2 of the word layout are tail-word eligible on their own.
+    Filtered and expired PUTs leave as tombstones, so run 0's version of the
+    key stays hidden.  Physical parity against an oracle that ingests the
+    window model's layout, then a full pass on both."""
+    rs = _window_rule_set("word")
+    m = make_model("word", rs)
+    merged, want = merge_window(m, 1, 2, NOW)
+    run0 = m.runs[0]
+    newest = {}
+    for run in m.runs[1:3]:
+        for k, (v, s, kd) in run.items():
+            if k not in newest or s > newest[k][1]:
+                newest[k] = (v, s, kd)
+    converted = [k for k, (v, s, kd) in merged.items() if kd == 1 and newest[k][2] == 0]
+    assert len(converted) == want["filtered"] + want["expired"]
+    # epoch-0 reads hide nothing by TTL: only the tombstone keeps run 0's PUT down
+    hidden = [k for k in converted if k in run0 and run0[k][2] == 0]
+    assert want["filtered"] > 0 and want["expired"] > 0 and len(hidden) > 2
+    rewritten = [k for k, (v, s, kd) in merged.items() if kd == 0 and v != newest[k][0]]
+    assert rewritten
+    g = open_part(hip_lib)
+    b = open_part(oracle_lib)
+    try:
+        g.set_envs({"engine.rank_mode": rank_mode})
+        for p in (g, b):
+            set_rule_envs(p, rs)
+        ingest_model(g, m)
+        err, got = g.compact_runs(1, 2, NOW)
+        assert err == OK
+        assert g.last_compact_route() == (rank, ROUTE_EMIT_CHUNKED)
+        assert stats_dict(got) == want
+        apply_window(m, 1, 2, NOW)
+        ingest_model(b, m)
+        assert (g.num_runs(), g.num_records()) == (b.num_runs(), b.num_records()) == \
+            (2, len(run0) + len(merged))
+        rows = drain(g, 0)
+        assert rows == drain(b, 0)
+        seen = {k for k, _, _ in rows}
+        for k in hidden:
+            assert k not in seen and g.get(k, 0) == (NOT_FOUND, None), k
+        eg, sg = g.manual_compact(NOW)
+        eb, sb = b.manual_compact(NOW)
+        assert eg == eb == OK and stats_dict(sg) == stats_dict(sb)
+        assert g.last_compact_route() == (rank, ROUTE_EMIT_CHUNKED_FIXED)
+        assert drain(g, 0) == drain(b, 0)
+    finally:
+        g.close()
+        b.close()
+
+
+# ======================= 2c: the CPU half =======================
+
+def test_route_entry_point_is_engine_only(oracle_part):
+    ext = open(os.path.join(REPO, "include", "rrdb_engine_ext.h")).read()
+    base = open(os.path.join(REPO, "include", "rrdb_engine.h")).read()
+    assert re.search(r"\bint32_t\s+rrdb_last_compact_route\s*\(\s*void\s*\*h,\s*"
+                     r"rrdb_compact_route\s*\*out\s*\)", ext)
+    assert "rrdb_last_compact_route" not in base
+    # the header's numbering is rank_mode's and emit_mode's, as capi.py mirrors it
+    for name, val in (("RRDB_ROUTE_NONE", ROUTE_NONE), ("RRDB_ROUTE_RANK_GLOBAL", G),
+                      ("RRDB_ROUTE_RANK_LDS", L), ("RRDB_ROUTE_RANK_LDST", T),
+                      ("RRDB_ROUTE_RANK_GRP", P), ("RRDB_ROUTE_EMIT_RANK", RK),
+                      ("RRDB_ROUTE_EMIT_INPUT", IN), ("RRDB_ROUTE_EMIT_CHUNKED", CH),
+                      ("RRDB_ROUTE_EMIT_CHUNKED_FIXED", FX)):
+        assert re.search(r"\b%s\s*=\s*%d\b" % (name, val), ext), name
+    if os.path.exists(HIP_SO):
+        assert hasattr(ctypes.CDLL(HIP_SO), "rrdb_last_compact_route")
+    assert not oracle_part.lib.has_compact_route
+    with pytest.raises(RuntimeError, match="rrdb_last_compact_route"):
+        oracle_part.last_compact_route()
+
+
+@pytest.mark.parametrize("layout", sorted(LAYOUTS))
+def test_oracle_against_pymodel(oracle_lib, layout):
+    """the two references agree on every rule set, stats and surviving bytes,
+    before the device is compared with them (reference() asserts it)"""
+    for rs in rule_sets(layout):
+        mstats, rows = reference(oracle_lib, layout, rs)
+        assert mstats["input_records"] == sum(len(r) for r in build_runs(layout))
+        assert mstats["output_records"] == len(rows) > 0
+    for version in (0, 2):
+        for rs in rule_sets(layout):
+            if rs.rewrite:
+                reference(oracle_lib, layout, rs, version)
+
+
+def _live(model):
+    """the newest version of every key, where it is a PUT: what the filter sees"""
+    newest = {}
+    for run in model.runs:
+        for k, (v, s, kd) in run.items():
+            if k not in newest or s > newest[k][1]:
+                newest[k] = (v, s, kd)
+    return {k: v for k, (v, s, kd) in newest.items() if kd == 0}
+
+
+def _matched(model, k, v):
+    """does the rule set touch this record, judged by pymodel alone: some
+    op's rules all match (on the post-default_ttl value, as the filter hands
+    it to them), or, for a set without ops, default_ttl applies"""
+    if not model.user_ops:
+        return expire_of(v, model.data_version) == 0
+    if model.default_ttl and expire_of(v, model.data_version) == 0:
+        off = 1 if model.data_version == 2 else 0
+        v = v[:off] + (NOW + model.default_ttl).to_bytes(4, "big") + v[off + 4:]
+    hk, sk = D.restore_key(k)
+    return any(model._all_rules_match(op, hk, sk, v, NOW) for op in model.user_ops)
+
+
+@pytest.mark.parametrize("layout", sorted(LAYOUTS))
+def test_rule_sets_are_what_they_claim(layout):
+    runs = build_runs(layout)
+    lay = LAYOUTS[layout]
+    # --- the layout ---
+    assert len(runs) == 3 and 200 <= sum(len(r) for r in runs) <= 400
+    keys = [{k for k, _, _, _ in r} for r in runs]
+    assert keys[0] & keys[1] and keys[1] & keys[2] and keys[0] & keys[2]  # shadowing
+    assert all(any(kd == 1 for _, _, _, kd in r) for r in runs)           # tombstones
+    live = _live(make_model(layout, rule_sets(layout)[0]))
+    exp = {expire_of(v, 1) for v in live.values()}
+    assert {0, NOW - 50, NOW + TTL_LO, NOW + TTL_HI, NOW + 500, NOW + 5000} <= exp
+    vlens = {len(v) for r in runs for _, v, _, kd in r if kd == 0}
+    klens = {len(k) for r in runs for k, _, _, _ in r}
+    if layout == "var":
+        assert len(klens) > 5 and len(vlens) > 3
+        sks = {D.restore_key(k)[1] for k in live}
+        shortest = min(len(p[1]) for p in lay.vocab)
+        assert b"" in sks and any(0 < len(s) < shortest for s in sks)
+    else:
+        # tail-word eligibility (HipEngine::word_eligible_range and
+        # build_tails): one stride >= 8, the first stride-8 bytes shared by
+        # every key of every run, and beyond them hashkey bytes that vary
+        assert klens == {16}
+        assert len({k[:8] for ks in keys for k in ks}) == 1
+        hklen = len(lay.hashkeys[0])
+        assert 8 < 2 + hklen < 16
+        assert all(len({k[8:2 + hklen] for k in ks}) > 1 for ks in keys)
+        assert all(len({k[2 + hklen:] for k in ks}) > 1 for ks in keys)
+        assert (len(vlens) == 1) == (layout == "word")
+    # --- the rule sets ---
+    names = [rs.name for rs in rule_sets(layout)]
+    assert len(set(names)) == len(names)
+    for rs in rule_sets(layout):
+        m = make_model(layout, rs)
+        assert rs.ops is None or len(m.user_ops) == rs.ops.count("COT_"), rs.name
+        live = _live(m)
+        n = sum(_matched(m, k, v) for k, v in live.items())
+        if rs.none:
+            assert n == 0, rs.name
+        else:
+            assert 0 < n < len(live), (rs.name, n, len(live))
+        surviving, stats = m.compact_full(NOW)
+        assert 0 < stats["output_records"], rs.name
+        changed = sum(expire_of(v, 1) != expire_of(live[k], 1) for k, (v, _) in surviving.items())
+        assert (changed > 0) == rs.rewrite, (rs.name, changed)
+    none = {rs.name for rs in rule_sets(layout) if rs.none}
+    assert none == {"hk_long_prefix", "hk_long_anywhere", "sk_long_postfix", "hk_empty_anywhere",
+                    "sk_empty_prefix", "sk_empty_postfix", "ttl_start_gt_stop", "ttl_stop_wraps"}
+    assert set(REWRITING) == {rs.name for rs in rule_sets(layout) if rs.rewrite}
+    # the cases a rewriting set is there for are in the data
+    v = lay.vocab
+    hk_pre = [k for k in live if D.restore_key(k)[0].startswith(v.prefix[0])]
+    assert {expire_of(live[k], 1) == 0 for k in hk_pre} == {True, False}  # FROM_CURRENT both ways
+    # the over-long patterns are made of bytes that are there
+    assert any(D.restore_key(k)[0] + D.restore_key(k)[1][:1] == v.long[0] for k in live)
+    assert any(D.restore_key(k)[0][-1:] + D.restore_key(k)[1] == v.long[1] for k in live)
+    # ANYWHERE-at-the-last-offset: where the pattern occurs, it occurs only there
+    for part in (0, 1):
+        hits = [D.restore_key(k)[part] for k in live if v.last[part] in D.restore_key(k)[part]]
+        assert hits and all(h.find(v.last[part]) == len(h) - len(v.last[part]) for h in hits)
