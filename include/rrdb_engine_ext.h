@@ -100,6 +100,57 @@
  *   - rrdb_phase_ms reports wb_sort, wb_emit and wb_total (device time), and
  *     wb_stage and wb_upload (host time of the staging and of the copies).
  *
+ * Batched counter increments.  The write service's read-modify-write family
+ * starts with incr (pegasus_write_service_impl.h:264-344): read the stored
+ * counter, add, store the decimal text.  rrdb_incr_batch takes n such ops
+ * unsorted, in commit order, duplicate keys allowed, and applies them on the
+ * device.  The call leaves behind exactly what this sequence leaves behind,
+ * ending in at most one new run: flush the memtable; for i = 0..n-1 apply
+ * incr op i as the reference does (its own read, then its own rrdb_put when
+ * it succeeds); rrdb_flush.
+ *   - Per op, with `old` the newest version of the key at that moment,
+ *     earlier ops of this batch included:
+ *       absent, tombstone or expired (expire > 0 && expire <= epoch_now):
+ *         new = increment, new_expire = directive > 0 ? directive : 0;
+ *       present with empty user data: new = increment, TTL as for "present";
+ *       present, user data not an integer: errors[i] = kInvalidArgument,
+ *         new_values[i] = 0, nothing is written;
+ *       present, integer, old + increment leaves int64: errors[i] =
+ *         kInvalidArgument, new_values[i] = old, nothing is written;
+ *       present, integer, the sum fits: new = old + increment.  TTL for
+ *         "present": directive 0 keeps the stored expire, < 0 clears it to 0,
+ *         > 0 sets it.
+ *   - "An integer" is what dsn::buf2int64 accepts: strtoll(s, &end, 0) in the
+ *     C locale over the whole span.  Optional leading isspace bytes, optional
+ *     sign, 0x/0X hex, leading-0 octal, else decimal; the whole span consumed
+ *     (an embedded NUL or a trailing byte fails); inside int64; at least one
+ *     digit ("0x", "09", "+", " " fail); no 0b prefix.
+ *   - A successful op stores rrdb_put(key, decimal(new), new_expire,
+ *     epoch_now): decimal is std::to_string (a '-' for negatives, no '+', no
+ *     padding), the header is that of the handle's pegasus.data_version with
+ *     timetag 0, and new_expire == 0 with a default_ttl env becomes
+ *     epoch_now + default_ttl.  errors[i] = kOk, new_values[i] = new.
+ *   - Only successful ops consume sequence numbers, as only they call
+ *     rrdb_put: the k-th successful op gets next_seq_floor + k and the floor
+ *     advances by `applied`.  Per key only the last successful op is stored,
+ *     as one PUT.  If no op succeeds no run is added and the floor is
+ *     unchanged; the call still returns kOk.
+ *   - Pending memtable entries are older than the batch: they are flushed
+ *     first into a run of their own, and a failure of that flush is returned.
+ *   - Everything is validated before anything changes.  kInvalidArgument with
+ *     the handle as before: offsets that do not start at 0 or decrease; a key
+ *     shorter than 2 bytes; hklen > klen - 2 or hklen == 0xFFFF;
+ *     increments == NULL; n_ops > 2^31 - 1; a split compaction or a pipelined
+ *     count scan pending.  n_ops == 0 is kOk and does nothing.
+ *   - Every allocation proportional to the batch may fail cleanly: on a full
+ *     device the call returns kIOError, no run is added, the floor is
+ *     unchanged, new_values / errors are unspecified, and a memtable flush
+ *     that already happened stays.
+ *   - rrdb_phase_ms reports incr_sort (sort and segments), incr_lookup,
+ *     incr_apply (chains and seqno ranks), incr_emit and incr_total (device
+ *     time).  Env "engine.incr_lane_max" (default 32) is the longest chain one
+ *     lane walks; a longer one is scanned by a whole wave.
+ *
  * Compaction route.  One compaction pass is a rank kernel followed by an emit
  * kernel, and which pair runs is decided per pass: from the envs
  * "engine.rank_mode" and "engine.emit_mode", the run count, the key shape of
@@ -207,6 +258,28 @@ int32_t rrdb_write_batch(void *h, uint64_t n_ops,
                          const uint8_t *values, const uint64_t *val_offs,
                          const uint32_t *expire_ts, const uint8_t *kinds,
                          uint32_t epoch_now, rrdb_write_batch_stats *stats);
+
+typedef struct {
+    uint64_t input_ops;      /* n_ops                                              */
+    uint64_t applied;        /* ops that wrote (errors[i] == kOk)                  */
+    uint64_t failed_parse;   /* old value not an integer / out of range            */
+    uint64_t failed_range;   /* old + increment leaves int64                       */
+    uint64_t output_records; /* records in the new run = distinct keys with >= 1 applied op */
+    uint64_t key_bytes, value_bytes; /* of the new run (values encoded)            */
+} rrdb_incr_batch_stats;
+
+/* Apply n_ops counter increments, given unsorted in commit order with
+ * duplicate keys allowed, on the device; see the header comment.  keys /
+ * key_offs: full rocksdb keys, packed, n+1 offsets.  increments[n].
+ * expire_ts_seconds[n]: the TTL directive of each op, may be null (all 0).
+ * new_values[n] / errors[n]: caller-owned, either may be null. */
+int32_t rrdb_incr_batch(void *h, uint64_t n_ops,
+                        const uint8_t *keys, const uint64_t *key_offs,
+                        const int64_t *increments,
+                        const int32_t *expire_ts_seconds,
+                        uint32_t epoch_now,
+                        int64_t *new_values, int32_t *errors,
+                        rrdb_incr_batch_stats *stats);
 
 enum {
     RRDB_ROUTE_NONE = -1,

@@ -144,6 +144,18 @@ class _WriteBatchStats(C.Structure):
     ]
 
 
+class _IncrBatchStats(C.Structure):
+    _fields_ = [
+        ("input_ops", C.c_uint64),
+        ("applied", C.c_uint64),
+        ("failed_parse", C.c_uint64),
+        ("failed_range", C.c_uint64),
+        ("output_records", C.c_uint64),
+        ("key_bytes", C.c_uint64),
+        ("value_bytes", C.c_uint64),
+    ]
+
+
 class _CompactRoute(C.Structure):
     _fields_ = [("rank", C.c_int32), ("emit", C.c_int32)]
 
@@ -152,6 +164,17 @@ class _CompactRoute(C.Structure):
 ROUTE_NONE = -1
 ROUTE_RANK_GLOBAL, ROUTE_RANK_LDS, ROUTE_RANK_LDST, ROUTE_RANK_GRP = 0, 1, 3, 4
 ROUTE_EMIT_RANK, ROUTE_EMIT_INPUT, ROUTE_EMIT_CHUNKED, ROUTE_EMIT_CHUNKED_FIXED = 0, 1, 2, 3
+
+
+@dataclass
+class IncrBatchStats:
+    input_ops: int = 0
+    applied: int = 0
+    failed_parse: int = 0
+    failed_range: int = 0
+    output_records: int = 0
+    key_bytes: int = 0
+    value_bytes: int = 0
 
 
 def _cslice(b: bytes, keep: list) -> _CSlice:
@@ -311,6 +334,12 @@ class RrdbLib:
             L.rrdb_write_batch.argtypes = [
                 C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                 C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(_WriteBatchStats)]
+        self.has_incr_batch = hasattr(L, "rrdb_incr_batch")
+        if self.has_incr_batch:
+            L.rrdb_incr_batch.restype = C.c_int32
+            L.rrdb_incr_batch.argtypes = [
+                C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(_IncrBatchStats)]
         self.has_compact_route = hasattr(L, "rrdb_last_compact_route")
         if self.has_compact_route:
             L.rrdb_last_compact_route.restype = C.c_int32
@@ -771,3 +800,51 @@ class RrdbPartition:
         expire = np.array([o[2] if o[1] is not None else 0 for o in ops], dtype=np.uint32)
         kinds = np.array([0 if o[1] is not None else 1 for o in ops], dtype=np.uint8)
         return self.write_batch_arrays(keys, koffs, vals, voffs, expire, kinds, epoch_now)
+
+    # ---- batched counter increments: engine-only (include/rrdb_engine_ext.h) ----
+    def _need_incr_batch(self):
+        if not self.lib.has_incr_batch:
+            raise RuntimeError(
+                f"incr_batch: backend {self.lib.backend!r} ({self.lib.path}) does not export "
+                "rrdb_incr_batch (engine-only extension)")
+
+    def incr_batch_arrays(self, keys_u8, key_offs_u64, increments_i64, expire_i32,
+                          epoch_now: int = 0):
+        """incr_batch from packed numpy arrays (no python loop; the bench and
+        the rejection tests, which hand in malformed arrays, use it).
+        expire_i32 may be None (every directive 0).  Returns
+        (err, new_values int64 array, errors int32 array, IncrBatchStats)."""
+        import numpy as np
+
+        self._need_incr_batch()
+        for a, dt in ((keys_u8, np.uint8), (key_offs_u64, np.uint64),
+                      (increments_i64, np.int64), (expire_i32, np.int32)):
+            assert a is None or (a.dtype == dt and a.flags["C_CONTIGUOUS"]), (a.dtype, dt)
+        n = len(increments_i64)
+        new_values = np.zeros(n, dtype=np.int64)
+        errors = np.zeros(n, dtype=np.int32)
+        st = _IncrBatchStats()
+        err = self._L.rrdb_incr_batch(
+            self._h, n,
+            keys_u8.ctypes.data_as(C.c_void_p), key_offs_u64.ctypes.data_as(C.c_void_p),
+            increments_i64.ctypes.data_as(C.c_void_p),
+            None if expire_i32 is None else expire_i32.ctypes.data_as(C.c_void_p),
+            epoch_now, new_values.ctypes.data_as(C.c_void_p),
+            errors.ctypes.data_as(C.c_void_p), C.byref(st))
+        stats = IncrBatchStats(**{f[0]: getattr(st, f[0]) for f in _IncrBatchStats._fields_})
+        return err, new_values, errors, stats
+
+    def incr_batch(self, ops, epoch_now: int = 0):
+        """Apply `ops`, a list of (full_key, increment, expire_directive) in
+        commit order (duplicate keys allowed: each op sees the ones before
+        it), as the reference's incr would, one after the other, on the
+        device.  Returns (err, new_values, errors, IncrBatchStats) with the
+        per-op results as python lists."""
+        import numpy as np
+
+        self._need_incr_batch()
+        keys, koffs = _pack([o[0] for o in ops])
+        inc = np.array([o[1] for o in ops], dtype=np.int64)
+        expire = np.array([o[2] for o in ops], dtype=np.int32)
+        err, nv, er, stats = self.incr_batch_arrays(keys, koffs, inc, expire, epoch_now)
+        return err, [int(x) for x in nv], [int(x) for x in er], stats

@@ -142,6 +142,15 @@ void launch_wb_scatter(const WbKeys &, const uint8_t *, const uint64_t *, uint64
                        const uint64_t *, const uint64_t *, const uint64_t *, uint64_t, uint64_t,
                        uint64_t, uint64_t, uint64_t *, uint64_t *, uint64_t *, uint64_t *,
                        uint64_t *, hipStream_t);
+void launch_incr_heads(const WbKeys &, uint64_t, const uint64_t *, const uint32_t *, uint64_t *,
+                       uint64_t *, hipStream_t);
+void launch_incr_segs(uint64_t, const uint64_t *, const uint64_t *, uint64_t *, uint64_t *,
+                      hipStream_t);
+void launch_incr_chain(const IncrArgs &, hipStream_t);
+void launch_incr_emit(const IncrArgs &, uint64_t, const uint64_t *, const uint64_t *,
+                      const uint64_t *, const uint64_t *, uint64_t, uint64_t, uint64_t, uint64_t,
+                      uint64_t, uint64_t, uint64_t *, uint64_t *, uint64_t *, uint64_t *,
+                      uint8_t *, hipStream_t);
 
 #define HIP_OK(x)                                                                                 \
     do {                                                                                           \
@@ -673,6 +682,9 @@ struct HipEngine {
      * which switches the tick off */
     uint32_t l0_trigger = 4;
     bool bulk_load = false;
+    /* rrdb_incr_batch: longest segment one lane walks (env
+     * "engine.incr_lane_max"); longer ones get a wave */
+    uint32_t incr_lane_max = INCR_LANE_MAX;
     bool bloom_enabled = true; /* env "rocksdb.filter_type": common(default)|none */
     uint32_t max_iter_count = 1000, mg_max_iter_count = 3000;
     uint64_t mg_max_iter_size = 30ull << 20, iter_time_ms = 30000;
@@ -1773,6 +1785,9 @@ int32_t rrdb_set_envs(void *h, const char *const *keys, const char *const *value
         } else if (k == "engine.l0_compaction_trigger") {
             long long t = atoll(v.c_str());
             e->l0_trigger = t < 2 ? 2u : (uint32_t)std::min<long long>(t, UINT32_MAX);
+        } else if (k == "engine.incr_lane_max") {
+            long long t = atoll(v.c_str());
+            e->incr_lane_max = t < 1 ? 1u : (uint32_t)std::min<long long>(t, 1 << 20);
         } else if (k == "rocksdb.usage_scenario") {
             /* bulk_load sets level0_file_num_compaction_trigger to -1, i.e.
              * no automatic compaction (set_usage_scenario); normal and
@@ -3942,6 +3957,50 @@ struct WbBufs {
     }
 };
 
+/* rrdb_incr_batch's sibling of WbBufs: its buffer sizes are all known, or
+ * bounded, once n and the key bytes are, so they are pieces of one try
+ * allocation (one hipMalloc and one hipFree per call instead of thirty) */
+struct IncrSlab {
+    uint8_t *base = nullptr;
+    uint64_t size = 0, used = 0;
+    bool ok = true;
+    /* before commit(): count the piece; after: hand it out.  Pieces are
+     * 256-byte aligned. */
+    template <typename T> void take(T **p, uint64_t bytes)
+    {
+        const uint64_t at = used;
+        used += (bytes + 255) & ~255ull;
+        if (base)
+            *p = used <= size ? (T *)(base + at) : nullptr;
+    }
+    bool commit()
+    {
+        size = used;
+        used = 0;
+        if (hipMalloc((void **)&base, size ? size : 1) != hipSuccess) {
+            (void)hipGetLastError();
+            base = nullptr;
+            ok = false;
+        }
+        return ok;
+    }
+    bool upload(void *dst, const void *src, uint64_t bytes)
+    {
+        if (!ok || !bytes)
+            return ok;
+        if (hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipGetLastError();
+            ok = false;
+        }
+        return ok;
+    }
+    ~IncrSlab()
+    {
+        if (base)
+            (void)hipFree(base);
+    }
+};
+
 extern "C" {
 
 int32_t rrdb_write_batch(void *h, uint64_t n_ops, const uint8_t *keys, const uint64_t *key_offs,
@@ -4103,6 +4162,245 @@ int32_t rrdb_write_batch(void *h, uint64_t n_ops, const uint8_t *keys, const uin
         stats->key_bytes = kbytes;
         stats->value_bytes = vbytes;
     }
+    return RRDB_OK;
+}
+
+/* ---- batched counter increments (rrdb_incr_batch, rrdb_engine_ext.h) ----
+ * The host validates and uploads keys, increments and directives once; the
+ * device sorts, looks the bases up, applies the chains and emits the run
+ * (kernels.hip, "incr batch").  Two read-backs: the totals before the run is
+ * allocated, the per-op results at the end. */
+static_assert(INCR_ERR_INVALID == RRDB_INVALID_ARGUMENT, "the chain kernels write this code");
+int32_t rrdb_incr_batch(void *h, uint64_t n_ops, const uint8_t *keys, const uint64_t *key_offs,
+                        const int64_t *increments, const int32_t *expire_ts_seconds,
+                        uint32_t epoch_now, int64_t *new_values, int32_t *errors,
+                        rrdb_incr_batch_stats *stats)
+{
+    if (stats)
+        *stats = rrdb_incr_batch_stats{};
+    if (!h)
+        return RRDB_INVALID_ARGUMENT;
+    auto *e = (HipEngine *)h;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (n_ops == 0)
+        return RRDB_OK;
+    if (e->pend.active || e->pend_scan.active)
+        return RRDB_INVALID_ARGUMENT;
+    if (!increments || !wb_keys_ok(n_ops, keys, key_offs))
+        return RRDB_INVALID_ARGUMENT;
+    const uint64_t n = n_ops;
+
+    /* pending memtable entries are older than the batch: their own run first */
+    e->activate();
+    int32_t rc = engine_flush(e);
+    if (rc != RRDB_OK)
+        return rc;
+
+    /* every buffer proportional to the batch is carved from one try
+     * allocation: the sizes are all known from n and the key bytes, the later
+     * ones (per segment, per output row) by their upper bound n */
+    const uint64_t in_fk = wb_fixed_stride(key_offs, n), in_kbytes = key_offs[n];
+    const int R = (int)e->runs.size();
+    IncrSlab b;
+    uint8_t *d_keys = nullptr;
+    uint64_t *d_koff = nullptr, *d_w0 = nullptr, *d_w1 = nullptr, *d_head = nullptr,
+             *d_hrank = nullptr, *d_seg_start = nullptr, *d_psc = nullptr, *d_hit = nullptr,
+             *d_ulen = nullptr, *d_ok = nullptr, *d_okrank = nullptr, *d_seg_has = nullptr,
+             *d_orank = nullptr, *d_seg_ksz = nullptr, *d_seg_vsz = nullptr, *d_red = nullptr,
+             *d_kpos = nullptr, *d_vpos = nullptr, *d_row_ksrc = nullptr, *d_kanch = nullptr;
+    int64_t *d_inc = nullptr, *d_newv = nullptr, *d_seg_val = nullptr;
+    int32_t *d_dir = nullptr, *d_status = nullptr, *d_err = nullptr;
+    uint32_t *d_lcp = nullptr, *d_i0 = nullptr, *d_i1 = nullptr, *d_expire = nullptr,
+             *d_seg_exp = nullptr, *d_seg_last = nullptr;
+    for (int pass = 0; pass < 2; pass++) { /* 0 sizes the slab, 1 hands the pieces out */
+        b.take(&d_keys, in_kbytes);
+        b.take(&d_koff, (n + 1) * 8); /* the lookup takes offsets */
+        b.take(&d_inc, n * 8);
+        b.take(&d_dir, n * 4);
+        b.take(&d_lcp, 256);
+        b.take(&d_w0, n * 8);
+        b.take(&d_w1, n * 8);
+        b.take(&d_i0, n * 4);
+        b.take(&d_i1, n * 4);
+        b.take(&d_head, n * 8);
+        b.take(&d_hrank, n * 8);
+        b.take(&d_seg_start, (n + 1) * 8);
+        b.take(&d_psc, psum_scratch_elems(n) * 8);
+        if (R) {
+            b.take(&d_status, n * 4);
+            b.take(&d_hit, n * 8);
+            b.take(&d_ulen, n * 8);
+            b.take(&d_expire, n * 4);
+        }
+        b.take(&d_newv, n * 8);
+        b.take(&d_err, n * 4);
+        b.take(&d_ok, n * 8);
+        b.take(&d_okrank, n * 8);
+        b.take(&d_seg_val, n * 8);
+        b.take(&d_seg_exp, n * 4);
+        b.take(&d_seg_last, n * 4);
+        b.take(&d_seg_has, n * 8);
+        b.take(&d_orank, n * 8);
+        b.take(&d_seg_ksz, n * 8);
+        b.take(&d_seg_vsz, n * 8);
+        b.take(&d_red, IR_WORDS * 8);
+        b.take(&d_kpos, n * 8);
+        b.take(&d_vpos, n * 8);
+        b.take(&d_row_ksrc, n * 8);
+        b.take(&d_kanch, (((in_kbytes + 15) >> 10) + 2) * 8);
+        if (pass == 0 && !b.commit())
+            return RRDB_IO_ERROR;
+    }
+    b.upload(d_keys, keys, in_kbytes);
+    b.upload(d_koff, key_offs, (n + 1) * 8);
+    b.upload(d_inc, increments, n * 8);
+    if (expire_ts_seconds) {
+        b.upload(d_dir, expire_ts_seconds, n * 4);
+    } else if (b.ok && hipMemset(d_dir, 0, n * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        b.ok = false;
+    }
+    if (!b.ok)
+        return RRDB_IO_ERROR;
+
+    hipEvent_t ev[6];
+    for (auto &x : ev)
+        HIP_OK(hipEventCreate(&x));
+    auto drop_events = [&] {
+        for (auto &x : ev)
+            (void)hipEventDestroy(x);
+    };
+    /* sort, then the segments: one per distinct key */
+    const WbKeys wk{d_keys, in_fk ? nullptr : d_koff, in_fk, d_lcp};
+    HIP_OK(hipEventRecord(ev[0], e->stream));
+    const int cur = launch_wb_sort(wk, n, d_lcp, d_w0, d_i0, d_w1, d_i1, e->stream);
+    const uint64_t *d_w = cur ? d_w1 : d_w0;
+    const uint32_t *d_ix = cur ? d_i1 : d_i0;
+    launch_incr_heads(wk, n, d_w, d_ix, d_head, d_red, e->stream);
+    launch_psum(d_head, d_hrank, n, d_psc, e->stream);
+    launch_incr_segs(n, d_head, d_hrank, d_seg_start, d_red, e->stream);
+    HIP_OK(hipEventRecord(ev[1], e->stream));
+
+    /* the bases: every op's key against the runs as they are now */
+    DevRun *dr = R ? e->dev_runs() : nullptr;
+    if (R)
+        launch_get(dr, R, d_keys, d_koff, n, epoch_now, e->data_version, d_status, d_hit, d_ulen,
+                   d_expire, e->stream);
+    HIP_OK(hipEventRecord(ev[2], e->stream));
+
+    IncrArgs a{};
+    a.k = wk;
+    a.n = n;
+    a.ix = d_ix;
+    a.seg_start = d_seg_start;
+    a.inc = d_inc;
+    a.dir = d_dir;
+    a.status = d_status;
+    a.hit = d_hit;
+    a.expire = d_expire;
+    a.runs = dr;
+    a.data_version = e->data_version;
+    a.epoch_now = epoch_now;
+    a.default_ttl = e->default_ttl;
+    a.lane_max = e->incr_lane_max;
+    a.new_val = d_newv;
+    a.err = d_err;
+    a.ok = d_ok;
+    a.seg_val = d_seg_val;
+    a.seg_exp = d_seg_exp;
+    a.seg_last = d_seg_last;
+    a.seg_has = d_seg_has;
+    a.seg_ksz = d_seg_ksz;
+    a.seg_vsz = d_seg_vsz;
+    a.red = (unsigned long long *)d_red;
+    launch_incr_chain(a, e->stream);
+    launch_psum(d_ok, d_okrank, n, d_psc, e->stream);
+    HIP_OK(hipEventRecord(ev[3], e->stream));
+
+    /* the totals: one read */
+    uint64_t red[IR_WORDS];
+    HIP_OK(hipMemcpyAsync(red, d_red, sizeof(red), hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipStreamSynchronize(e->stream));
+    const uint64_t n_seg = red[IR_NSEG], n_out = red[IR_NOUT];
+    const uint64_t kbytes = red[IR_KBYTES], vbytes = red[IR_VBYTES];
+    auto u32_or_0 = [](uint64_t v) { return v > UINT32_MAX ? 0u : (uint32_t)v; };
+    const uint32_t out_fk = n_out && red[IR_KMIN] == red[IR_KMAX] ? u32_or_0(red[IR_KMIN]) : 0;
+    const uint32_t out_fv = n_out && red[IR_VMIN] == red[IR_VMAX] ? u32_or_0(red[IR_VMIN]) : 0;
+
+    auto results_out = [&]() {
+        if (new_values)
+            HIP_OK(hipMemcpy(new_values, d_newv, n * 8, hipMemcpyDeviceToHost));
+        if (errors)
+            HIP_OK(hipMemcpy(errors, d_err, n * 4, hipMemcpyDeviceToHost));
+        if (stats) {
+            stats->input_ops = n;
+            stats->applied = red[IR_APPLIED];
+            stats->failed_parse = red[IR_FPARSE];
+            stats->failed_range = red[IR_FRANGE];
+            stats->output_records = n_out;
+            stats->key_bytes = kbytes;
+            stats->value_bytes = vbytes;
+        }
+    };
+    auto timers = [&](bool emitted) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
+            e->phase_ms["incr_sort"] = ms;
+        if (hipEventElapsedTime(&ms, ev[1], ev[2]) == hipSuccess)
+            e->phase_ms["incr_lookup"] = ms;
+        if (hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess)
+            e->phase_ms["incr_apply"] = ms;
+        e->phase_ms["incr_emit"] = 0.0;
+        if (emitted && hipEventElapsedTime(&ms, ev[4], ev[5]) == hipSuccess)
+            e->phase_ms["incr_emit"] = ms;
+        float tot = 0;
+        if (hipEventElapsedTime(&tot, ev[0], ev[3]) == hipSuccess)
+            e->phase_ms["incr_total"] = tot + e->phase_ms["incr_emit"];
+    };
+    if (n_out == 0) { /* no op wrote: no run, the floor stays */
+        timers(false);
+        drop_events();
+        results_out();
+        return RRDB_OK;
+    }
+
+    RunBuf r;
+    if (out_fk)
+        d_kpos = nullptr;
+    if (out_fv)
+        d_vpos = nullptr;
+    if (n_seg > n || n_out > n_seg || kbytes > in_kbytes ||
+        !e->alloc_base(r, n_out, kbytes, vbytes, RunAlloc::Try)) {
+        drop_events();
+        return RRDB_IO_ERROR;
+    }
+    /* the strides detect_fixed_* would report for the emitted run: all PUTs */
+    r.fixed_klen = out_fk;
+    r.fixed_vlen = out_fv;
+    r.fixed_vlen_put = out_fv;
+    HIP_OK(hipEventRecord(ev[4], e->stream));
+    launch_psum(d_seg_has, d_orank, n_seg, d_psc, e->stream);
+    if (d_kpos)
+        launch_psum(d_seg_ksz, d_kpos, n_seg, d_psc, e->stream);
+    if (d_vpos)
+        launch_psum(d_seg_vsz, d_vpos, n_seg, d_psc, e->stream);
+    launch_incr_emit(a, n_seg, d_okrank, d_orank, d_kpos, d_vpos, e->next_seq_floor, n_out, kbytes,
+                     vbytes, out_fk, out_fv, r.koff, r.voff, r.sk, d_row_ksrc, r.vals, e->stream);
+    launch_split_copy(d_row_ksrc, r.koff, n_out, r.fixed_klen, kbytes, d_kanch, r.keys,
+                      e->stream);
+    HIP_OK(hipEventRecord(ev[5], e->stream));
+    if (!e->finish_run(r, nullptr, RunAlloc::Try, e->bloom_enabled)) {
+        e->free_run(r);
+        drop_events();
+        return RRDB_IO_ERROR;
+    }
+    timers(true);
+    drop_events();
+
+    e->runs.push_back(r);
+    e->runs_changed();
+    e->next_seq_floor += red[IR_APPLIED];
+    results_out();
     return RRDB_OK;
 }
 

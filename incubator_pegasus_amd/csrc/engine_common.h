@@ -49,6 +49,51 @@ enum {
     WBR_KMIN = 0, WBR_KMAX, WBR_VMIN, WBR_VMAX, WBR_PVMIN, WBR_PVMAX, WBR_PUTS, WBR_WORDS
 };
 
+struct DevRun;
+
+/* incr batch (rrdb_incr_batch).  The ops of one key form a segment of the
+ * sorted batch.  A segment of up to INCR_LANE_MAX ops is walked by one lane;
+ * a longer one (a hot counter) gets a whole wave.  Env "engine.incr_lane_max"
+ * overrides it per handle (tools/bench_incr_batch.py sweeps it). */
+#define INCR_LANE_MAX 32
+
+/* incr-batch reduction (one block of u64 words, vector atomics) */
+enum {
+    IR_NSEG = 0, IR_APPLIED, IR_FPARSE, IR_FRANGE, IR_NOUT, IR_KBYTES, IR_VBYTES,
+    IR_KMIN, IR_KMAX, IR_VMIN, IR_VMAX, IR_WORDS
+};
+
+#define INCR_NO_OP 0xFFFFFFFFu
+/* errors[i] of a failed op: RRDB_INVALID_ARGUMENT (engine.cpp asserts the two agree) */
+#define INCR_ERR_INVALID 4
+
+/* everything the chain and emit kernels of rrdb_incr_batch share, by value */
+struct IncrArgs {
+    WbKeys k;              /* the uploaded keys, op order                       */
+    uint64_t n;            /* ops                                               */
+    const uint32_t *ix;    /* [n] sorted position -> op (key asc, op desc)      */
+    const uint64_t *seg_start; /* [n_seg + 1] sorted position of each segment  */
+    const int64_t *inc;    /* [n] op order                                      */
+    const int32_t *dir;    /* [n] expire directive, op order                    */
+    /* the lookup of every op's key against the runs (launch_get), op order;
+     * status null = the handle has no run, every base is absent */
+    const int32_t *status;
+    const uint64_t *hit;
+    const uint32_t *expire;
+    const DevRun *runs;
+    uint32_t data_version, epoch_now, default_ttl, lane_max;
+    /* per op, op order */
+    int64_t *new_val;
+    int32_t *err;
+    uint64_t *ok;          /* 1 = the op wrote                                  */
+    /* per segment */
+    int64_t *seg_val;      /* value after the last successful op                */
+    uint32_t *seg_exp;     /* its stored expire                                 */
+    uint32_t *seg_last;    /* that op, INCR_NO_OP when none succeeded           */
+    uint64_t *seg_has, *seg_ksz, *seg_vsz;
+    unsigned long long *red; /* IR_* */
+};
+
 /* device-visible descriptor of one sorted run */
 struct DevRun {
     const uint8_t *keys;

@@ -3994,3 +3994,445 @@ void launch_wb_scatter(const WbKeys &k, const uint8_t *d_svals, const uint64_t *
         k, d_svals, d_svoff, fv, d_kinds, n, d_ix, d_keep, d_rank, d_kpos, d_vpos, seq_floor,
         n_out, kbytes, vbytes, d_okoff, d_ovoff, d_osk, d_row_ksrc, d_row_vsrc);
 }
+
+/* ================= incr batch (rrdb_incr_batch) =================
+ * n counter increments, unsorted, duplicate keys allowed, applied as the
+ * sequence get + put per op would apply them, ending in one run:
+ *   sort:     launch_wb_sort, unchanged.  Within a key the ops stand newest
+ *             first, so a chain is walked from the segment's end to its start.
+ *   segments: head flags (the write batch's keep rule), launch_psum, then the
+ *             sorted position where every segment starts.
+ *   lookup:   launch_get with the expire output on the uploaded op arrays.
+ *   chain:    every segment takes its base from the lookup (absent, empty, an
+ *             integer, or text that is no integer: incr_num.h) and applies its
+ *             ops in order.  A segment of up to lane_max ops is walked by one
+ *             lane, exactly as the reference walks it.  A longer one gets a
+ *             wave: the value after op j is base + the prefix sum of the
+ *             increments, scanned 64 at a time in 128 bits with a carried
+ *             total, and the TTL state is "the last non-zero directive wins",
+ *             scanned the same way.  That holds as long as no prefix leaves
+ *             int64 and no op stores an expire that is already past; a first
+ *             pass checks it, and a segment that fails the check, or whose
+ *             base does not parse, is walked by lane 0 instead.
+ *   rank:     launch_psum of the ok flags in op order gives the seqnos, of
+ *             "segment has an ok op" the output row.
+ *   emit:     header + decimal straight into the value column; sk, offsets
+ *             and key sources by row, keys through launch_split_copy.
+ * Every result is a function of the sorted order alone, so it does not depend
+ * on the grid or on scheduling. */
+#include "incr_num.h"
+
+enum { INCR_ABSENT = 0, INCR_EMPTY = 1, INCR_INT = 2, INCR_INVALID = 3 };
+
+struct IncrBase {
+    int kind;
+    int64_t val;
+    uint32_t expire;
+};
+
+struct IncrTally {
+    unsigned long long applied = 0, fparse = 0, frange = 0, nout = 0, kbytes = 0, vbytes = 0;
+    unsigned long long kmin = ~0ull, kmax = 0, vmin = ~0ull, vmax = 0;
+};
+
+/* head[p] = 1 iff sorted position p starts a key */
+__global__ void __launch_bounds__(BLOCK)
+    k_incr_heads(WbKeys k, uint64_t n, const uint64_t *w, const uint32_t *ix, uint64_t *head)
+{
+    const uint64_t L = *k.lcp;
+    for (uint64_t p = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; p < n;
+         p += gridDim.x * (uint64_t)blockDim.x)
+        head[p] = (p == 0 || w[p] != w[p - 1] || wb_tail_cmp(k, L, ix[p - 1], ix[p]) != 0) ? 1 : 0;
+}
+
+/* seg_start[s] for every segment, seg_start[n_seg] = n, red[IR_NSEG] = n_seg */
+__global__ void __launch_bounds__(BLOCK)
+    k_incr_segs(uint64_t n, const uint64_t *head, const uint64_t *hrank, uint64_t *seg_start,
+                unsigned long long *red)
+{
+    for (uint64_t p = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; p < n;
+         p += gridDim.x * (uint64_t)blockDim.x) {
+        if (head[p])
+            seg_start[hrank[p]] = p;
+        if (p == n - 1) {
+            const uint64_t ns = hrank[p] + head[p];
+            seg_start[ns] = n; /* ns <= n: the column has n + 1 entries */
+            red[IR_NSEG] = ns;
+        }
+    }
+}
+
+/* the newest stored version of op i's key, as the lookup found it */
+__device__ static inline IncrBase incr_base(const IncrArgs &a, uint32_t i)
+{
+    IncrBase b{INCR_ABSENT, 0, 0};
+    if (!a.status || a.status[i] != 0)
+        return b; /* absent, tombstone or expired */
+    const uint64_t id = a.hit[i];
+    uint64_t vl;
+    const uint8_t *v = run_val(a.runs[id >> 40], id & 0xFFFFFFFFFFull, &vl);
+    const uint32_t hdr = dev_hdr_len(a.data_version);
+    b.expire = a.expire[i];
+    if (vl <= hdr)
+        b.kind = INCR_EMPTY;
+    else
+        b.kind = incr_parse_i64(v + hdr, vl - hdr, &b.val) ? INCR_INT : INCR_INVALID;
+    return b;
+}
+
+/* the TTL rule of a present record; then rrdb_put's write-time default_ttl */
+__device__ static inline uint32_t incr_present_expire(int32_t d, uint32_t stored)
+{
+    return d == 0 ? stored : (d < 0 ? 0u : (uint32_t)d);
+}
+__device__ static inline uint32_t incr_stored_expire(const IncrArgs &a, uint32_t e)
+{
+    return (e == 0 && a.default_ttl != 0) ? a.epoch_now + a.default_ttl : e;
+}
+
+/* what segment s leaves behind */
+__device__ static inline void incr_seg_out(const IncrArgs &a, uint64_t s, uint32_t last,
+                                           int64_t val, uint32_t exp, IncrTally &t)
+{
+    a.seg_last[s] = last;
+    a.seg_val[s] = val;
+    a.seg_exp[s] = exp;
+    uint64_t kl = 0, vl = 0;
+    if (last != INCR_NO_OP) {
+        (void)wb_key(a.k, last, &kl);
+        vl = dev_hdr_len(a.data_version) + incr_dec_len(val);
+        t.nout++;
+        t.kbytes += kl;
+        t.vbytes += vl;
+        t.kmin = kl < t.kmin ? kl : t.kmin;
+        t.kmax = kl > t.kmax ? kl : t.kmax;
+        t.vmin = vl < t.vmin ? vl : t.vmin;
+        t.vmax = vl > t.vmax ? vl : t.vmax;
+    }
+    a.seg_has[s] = last != INCR_NO_OP ? 1 : 0;
+    a.seg_ksz[s] = kl;
+    a.seg_vsz[s] = vl;
+}
+
+/* segment s = sorted positions [beg, end), walked oldest op first by one
+ * lane: the reference's incr, op by op */
+__device__ static void incr_walk(const IncrArgs &a, uint64_t s, uint64_t beg, uint64_t end,
+                                 IncrBase b, IncrTally &t)
+{
+    int kind = b.kind;
+    int64_t cur = b.val;
+    uint32_t exp = b.expire, last = INCR_NO_OP;
+    for (uint64_t q = end; q-- > beg;) {
+        const uint32_t i = a.ix[q];
+        const int64_t inc = a.inc[i];
+        const int32_t d = a.dir[i];
+        int64_t nv = inc;
+        uint32_t ne;
+        if (kind == INCR_ABSENT || dev_ts_expired(a.epoch_now, exp)) {
+            ne = d > 0 ? (uint32_t)d : 0u;
+        } else if (kind == INCR_EMPTY) {
+            ne = incr_present_expire(d, exp);
+        } else if (kind == INCR_INVALID) {
+            a.new_val[i] = 0;
+            a.err[i] = INCR_ERR_INVALID;
+            a.ok[i] = 0;
+            t.fparse++;
+            continue;
+        } else {
+            if (!incr_safe_add(cur, inc, &nv)) {
+                a.new_val[i] = cur;
+                a.err[i] = INCR_ERR_INVALID;
+                a.ok[i] = 0;
+                t.frange++;
+                continue;
+            }
+            ne = incr_present_expire(d, exp);
+        }
+        cur = nv;
+        exp = incr_stored_expire(a, ne);
+        kind = INCR_INT;
+        last = i;
+        a.new_val[i] = nv;
+        a.err[i] = 0;
+        a.ok[i] = 1;
+        t.applied++;
+    }
+    incr_seg_out(a, s, last, cur, exp, t);
+}
+
+/* block-level then device-level fold of the per-thread tallies */
+__device__ static inline void incr_tally_flush(const IncrTally &t, unsigned long long *s_red,
+                                               unsigned long long *red)
+{
+    if (threadIdx.x < IR_WORDS)
+        s_red[threadIdx.x] = (threadIdx.x == IR_KMIN || threadIdx.x == IR_VMIN) ? ~0ull : 0ull;
+    __syncthreads();
+    if (t.applied)
+        atomicAdd(&s_red[IR_APPLIED], t.applied);
+    if (t.fparse)
+        atomicAdd(&s_red[IR_FPARSE], t.fparse);
+    if (t.frange)
+        atomicAdd(&s_red[IR_FRANGE], t.frange);
+    if (t.nout) {
+        atomicAdd(&s_red[IR_NOUT], t.nout);
+        atomicAdd(&s_red[IR_KBYTES], t.kbytes);
+        atomicAdd(&s_red[IR_VBYTES], t.vbytes);
+        atomicMin(&s_red[IR_KMIN], t.kmin);
+        atomicMax(&s_red[IR_KMAX], t.kmax);
+        atomicMin(&s_red[IR_VMIN], t.vmin);
+        atomicMax(&s_red[IR_VMAX], t.vmax);
+    }
+    __syncthreads();
+    if (threadIdx.x > IR_NSEG && threadIdx.x < IR_WORDS) {
+        const unsigned long long v = s_red[threadIdx.x];
+        if (threadIdx.x == IR_KMIN || threadIdx.x == IR_VMIN)
+            atomicMin(&red[threadIdx.x], v);
+        else if (threadIdx.x == IR_KMAX || threadIdx.x == IR_VMAX)
+            atomicMax(&red[threadIdx.x], v);
+        else if (v)
+            atomicAdd(&red[threadIdx.x], v);
+    }
+}
+
+/* segments of up to lane_max ops: one lane each */
+__global__ void __launch_bounds__(BLOCK) k_incr_chain_lane(IncrArgs a)
+{
+    __shared__ unsigned long long s_red[IR_WORDS];
+    IncrTally t;
+    const uint64_t ns = a.red[IR_NSEG];
+    for (uint64_t s = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; s < ns;
+         s += gridDim.x * (uint64_t)blockDim.x) {
+        const uint64_t beg = a.seg_start[s], end = a.seg_start[s + 1];
+        if (end <= beg || end > a.n || end - beg > a.lane_max)
+            continue;
+        incr_walk(a, s, beg, end, incr_base(a, a.ix[beg]), t);
+    }
+    incr_tally_flush(t, s_red, a.red);
+}
+
+__device__ static inline __int128 incr_shfl_up128(__int128 v, int off)
+{
+    unsigned long long lo = (unsigned long long)v, hi = (unsigned long long)(v >> 64);
+    lo = __shfl_up(lo, off, WAVE);
+    hi = __shfl_up(hi, off, WAVE);
+    return (__int128)(((unsigned __int128)hi << 64) | lo);
+}
+__device__ static inline __int128 incr_bcast128(__int128 v, int src)
+{
+    unsigned long long lo = (unsigned long long)v, hi = (unsigned long long)(v >> 64);
+    lo = __shfl(lo, src, WAVE);
+    hi = __shfl(hi, src, WAVE);
+    return (__int128)(((unsigned __int128)hi << 64) | lo);
+}
+
+/* one stride of 64 ops of a chain: lane l holds chain position c*64 + l.
+ * *sum becomes carry + the inclusive prefix of the increments, *dd the last
+ * non-zero directive at or before the lane (0 = none yet); the carries move
+ * on to the next stride.  Every lane of the wave calls this. */
+__device__ static inline void incr_stride_scan(int lane, int64_t inc, int32_t d, __int128 *carry,
+                                               int32_t *carry_d, __int128 *sum, int32_t *dd)
+{
+    __int128 v = inc;
+    int32_t x = d;
+    for (int off = 1; off < WAVE; off <<= 1) {
+        const __int128 up = incr_shfl_up128(v, off);
+        const int32_t xu = __shfl_up(x, off, WAVE);
+        if (lane >= off) {
+            v += up;
+            x = x != 0 ? x : xu;
+        }
+    }
+    *sum = *carry + v;
+    *dd = x != 0 ? x : *carry_d;
+    *carry = incr_bcast128(*sum, WAVE - 1);
+    *carry_d = __shfl(*dd, WAVE - 1, WAVE);
+}
+
+/* one pass of a wave over the chain of segment [beg, end), oldest op first,
+ * INCR_WAVE_UNROLL strides of 64 at a time: the op indices of all of them are
+ * loaded first, then their increments and directives, then the scans run, so
+ * that the two dependent loads of a stride overlap with its neighbours'
+ * instead of standing in front of every scan.  WRITE = false checks whether
+ * the sequential walk would ever fail or reset and returns that per lane;
+ * WRITE = true stores the running sums as the answers. */
+#define INCR_WAVE_UNROLL 4
+template <bool WRITE>
+__device__ static inline bool incr_wave_pass(const IncrArgs &a, uint64_t s, uint64_t beg,
+                                             uint64_t end, const IncrBase &b, int lane,
+                                             IncrTally &t)
+{
+    const uint64_t len = end - beg;
+    const __int128 lo128 = INT64_MIN, hi128 = INT64_MAX;
+    const uint32_t e0 = b.kind == INCR_ABSENT ? 0u : b.expire;
+    __int128 carry = b.kind == INCR_INT ? (__int128)b.val : (__int128)0;
+    int32_t carry_d = 0;
+    bool bad = false;
+    for (uint64_t c = 0; c < len; c += WAVE * INCR_WAVE_UNROLL) {
+        uint32_t iu[INCR_WAVE_UNROLL];
+        int64_t incu[INCR_WAVE_UNROLL];
+        int32_t du[INCR_WAVE_UNROLL];
+#pragma unroll
+        for (int u = 0; u < INCR_WAVE_UNROLL; u++) {
+            const uint64_t q = c + (uint64_t)u * WAVE + lane; /* chain position */
+            iu[u] = q < len ? a.ix[end - 1 - q] : INCR_NO_OP;
+        }
+#pragma unroll
+        for (int u = 0; u < INCR_WAVE_UNROLL; u++) {
+            const bool in = iu[u] != INCR_NO_OP;
+            incu[u] = in ? a.inc[iu[u]] : 0;
+            du[u] = in ? a.dir[iu[u]] : 0;
+        }
+#pragma unroll
+        for (int u = 0; u < INCR_WAVE_UNROLL; u++) {
+            if (c + (uint64_t)u * WAVE >= len)
+                break; /* the same in every lane */
+            const bool in = iu[u] != INCR_NO_OP;
+            __int128 sum;
+            int32_t dd;
+            incr_stride_scan(lane, incu[u], du[u], &carry, &carry_d, &sum, &dd);
+            if (!in)
+                continue;
+            if (!WRITE) {
+                bad |= sum < lo128 || sum > hi128 ||
+                       (du[u] > 0 && (uint32_t)du[u] <= a.epoch_now);
+                continue;
+            }
+            a.new_val[iu[u]] = (int64_t)sum;
+            a.err[iu[u]] = 0;
+            a.ok[iu[u]] = 1;
+            if (c + (uint64_t)u * WAVE + lane == len - 1) /* the newest op: position beg */
+                incr_seg_out(a, s, iu[u], (int64_t)sum,
+                             incr_stored_expire(a, incr_present_expire(dd, e0)), t);
+        }
+    }
+    return bad;
+}
+
+/* a long segment on a whole wave; every lane enters with the same s */
+__device__ static void incr_seg_wave(const IncrArgs &a, uint64_t s, int lane, IncrTally &t)
+{
+    const uint64_t beg = a.seg_start[s], end = a.seg_start[s + 1];
+    if (end <= beg || end > a.n)
+        return;
+    const IncrBase b = incr_base(a, a.ix[beg]); /* same address in every lane */
+    bool bad = b.kind == INCR_INVALID ||
+               (a.default_ttl != 0 && dev_ts_expired(a.epoch_now, a.epoch_now + a.default_ttl));
+    if (!bad)
+        bad = incr_wave_pass<false>(a, s, beg, end, b, lane, t);
+    if (__any(bad)) {
+        if (lane == 0)
+            incr_walk(a, s, beg, end, b, t);
+        return;
+    }
+    (void)incr_wave_pass<true>(a, s, beg, end, b, lane, t);
+    if (lane == 0)
+        t.applied += end - beg;
+}
+
+/* segments longer than lane_max: a wave each.  A wave looks at 64 segments
+ * at a time, one per lane, and takes the long ones among them in turn. */
+__global__ void __launch_bounds__(BLOCK) k_incr_chain_wave(IncrArgs a)
+{
+    __shared__ unsigned long long s_red[IR_WORDS];
+    IncrTally t;
+    const int lane = threadIdx.x & (WAVE - 1);
+    const uint64_t ns = a.red[IR_NSEG];
+    const uint64_t n_waves = (gridDim.x * (uint64_t)blockDim.x) / WAVE;
+    for (uint64_t c = (blockIdx.x * (uint64_t)blockDim.x + threadIdx.x) / WAVE; c * WAVE < ns;
+         c += n_waves) {
+        const uint64_t s = c * WAVE + lane;
+        const bool is_long = s < ns && a.seg_start[s + 1] - a.seg_start[s] > a.lane_max;
+        unsigned long long m = __ballot(is_long);
+        while (m) {
+            const int l = __ffsll((long long)m) - 1;
+            m &= m - 1;
+            incr_seg_wave(a, c * WAVE + l, lane, t);
+        }
+    }
+    incr_tally_flush(t, s_red, a.red);
+}
+
+/* the output rows: segment s with an ok op becomes row orank[s].  sk, 0-based
+ * okoff/ovoff (n_out+1 entries), the key's source address, and the value
+ * itself: the header of the data version (timetag 0) + the decimal text.
+ * fk / fv != 0: the offset is row x stride; else kpos / vpos hold it. */
+__global__ void __launch_bounds__(BLOCK)
+    k_incr_emit(IncrArgs a, const uint64_t *okrank, const uint64_t *orank, const uint64_t *kpos,
+                const uint64_t *vpos, uint64_t seq_floor, uint64_t n_out, uint64_t kbytes,
+                uint64_t vbytes, uint64_t fk, uint64_t fv, uint64_t *okoff, uint64_t *ovoff,
+                uint64_t *osk, uint64_t *row_ksrc, uint8_t *ovals)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        okoff[n_out] = kbytes;
+        ovoff[n_out] = vbytes;
+    }
+    const uint64_t ns = a.red[IR_NSEG];
+    const uint32_t hdr = dev_hdr_len(a.data_version);
+    for (uint64_t s = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; s < ns;
+         s += gridDim.x * (uint64_t)blockDim.x) {
+        if (!a.seg_has[s])
+            continue;
+        const uint64_t r = orank[s];
+        const uint32_t i = a.seg_last[s];
+        const uint64_t vo = fv ? r * fv : vpos[s];
+        if (r >= n_out || i >= a.n || vo + a.seg_vsz[s] > vbytes)
+            continue; /* cannot happen: the totals come from the same columns */
+        osk[r] = (seq_floor + okrank[i]) << 1; /* a PUT */
+        okoff[r] = fk ? r * fk : kpos[s];
+        ovoff[r] = vo;
+        uint64_t kl;
+        row_ksrc[r] = (uint64_t)wb_key(a.k, i, &kl);
+        uint8_t *v = ovals + vo;
+        for (uint32_t j = 0; j < hdr; j++)
+            v[j] = 0;
+        const uint32_t off = a.data_version == 2 ? 1 : 0;
+        if (a.data_version == 2)
+            v[0] = 0x82;
+        const uint32_t ts = a.seg_exp[s];
+        v[off] = (uint8_t)(ts >> 24);
+        v[off + 1] = (uint8_t)(ts >> 16);
+        v[off + 2] = (uint8_t)(ts >> 8);
+        v[off + 3] = (uint8_t)ts;
+        (void)incr_format_i64(a.seg_val[s], v + hdr); /* seg_vsz[s] - hdr bytes */
+    }
+}
+
+/* head flags and, after the caller's launch_psum of them into d_hrank, the
+ * segment starts.  d_red: IR_WORDS u64 words, initialised here. */
+void launch_incr_heads(const WbKeys &k, uint64_t n, const uint64_t *d_w, const uint32_t *d_ix,
+                       uint64_t *d_head, uint64_t *d_red, hipStream_t s)
+{
+    uint64_t init[IR_WORDS];
+    for (int j = 0; j < IR_WORDS; j++)
+        init[j] = (j == IR_KMIN || j == IR_VMIN) ? ~0ull : 0ull;
+    HIP_CHECK(hipMemcpyAsync(d_red, init, sizeof(init), hipMemcpyHostToDevice, s));
+    k_incr_heads<<<grid_for(n, BLOCK), BLOCK, 0, s>>>(k, n, d_w, d_ix, d_head);
+}
+
+void launch_incr_segs(uint64_t n, const uint64_t *d_head, const uint64_t *d_hrank,
+                      uint64_t *d_seg_start, uint64_t *d_red, hipStream_t s)
+{
+    k_incr_segs<<<grid_for(n, BLOCK), BLOCK, 0, s>>>(n, d_head, d_hrank, d_seg_start,
+                                                    (unsigned long long *)d_red);
+}
+
+/* both chain kernels; the segment count is read on the device, so the grids
+ * are sized by the op count, which bounds it */
+void launch_incr_chain(const IncrArgs &a, hipStream_t s)
+{
+    k_incr_chain_lane<<<grid_for(a.n, BLOCK), BLOCK, 0, s>>>(a);
+    /* at most n / lane_max segments are long, and a wave takes one at a time */
+    k_incr_chain_wave<<<grid_for((a.n / (a.lane_max + 1ull) + 1) * WAVE, BLOCK), BLOCK, 0, s>>>(a);
+}
+
+void launch_incr_emit(const IncrArgs &a, uint64_t n_seg, const uint64_t *d_okrank,
+                      const uint64_t *d_orank, const uint64_t *d_kpos, const uint64_t *d_vpos,
+                      uint64_t seq_floor, uint64_t n_out, uint64_t kbytes, uint64_t vbytes,
+                      uint64_t fk, uint64_t fv, uint64_t *d_okoff, uint64_t *d_ovoff,
+                      uint64_t *d_osk, uint64_t *d_row_ksrc, uint8_t *d_ovals, hipStream_t s)
+{
+    k_incr_emit<<<grid_for(n_seg, BLOCK), BLOCK, 0, s>>>(a, d_okrank, d_orank, d_kpos, d_vpos,
+                                                        seq_floor, n_out, kbytes, vbytes, fk, fv,
+                                                        d_okoff, d_ovoff, d_osk, d_row_ksrc,
+                                                        d_ovals);
+}

@@ -29,15 +29,12 @@ static inline bool wb_offsets_ok(const uint64_t *offs, uint64_t n)
     return true;
 }
 
-/* everything rrdb_write_batch rejects that does not depend on the handle.
- * Reads keys only inside spans the offsets have already proven ordered. */
-static inline bool wb_validate(uint64_t n, const uint8_t *keys, const uint64_t *key_offs,
-                               const uint8_t *values, const uint64_t *val_offs,
-                               const uint8_t *kinds)
+/* n full keys [u16 BE hklen][hashkey][sortkey]: the op count, the offsets and
+ * every key's shape (rrdb_write_batch and rrdb_incr_batch share it).  Reads
+ * keys only inside spans the offsets have already proven ordered. */
+static inline bool wb_keys_ok(uint64_t n, const uint8_t *keys, const uint64_t *key_offs)
 {
-    if (n == 0 || n > WB_MAX_OPS || !keys || !kinds)
-        return false;
-    if (!wb_offsets_ok(key_offs, n) || !wb_offsets_ok(val_offs, n))
+    if (n == 0 || n > WB_MAX_OPS || !keys || !wb_offsets_ok(key_offs, n))
         return false;
     for (uint64_t i = 0; i < n; i++) {
         const uint64_t kl = key_offs[i + 1] - key_offs[i];
@@ -47,6 +44,18 @@ static inline bool wb_validate(uint64_t n, const uint8_t *keys, const uint64_t *
         const uint64_t hl = ((uint64_t)k[0] << 8) | k[1];
         if (hl == 0xFFFFull || hl > kl - 2)
             return false;
+    }
+    return true;
+}
+
+/* everything rrdb_write_batch rejects that does not depend on the handle */
+static inline bool wb_validate(uint64_t n, const uint8_t *keys, const uint64_t *key_offs,
+                               const uint8_t *values, const uint64_t *val_offs,
+                               const uint8_t *kinds)
+{
+    if (!kinds || !wb_keys_ok(n, keys, key_offs) || !wb_offsets_ok(val_offs, n))
+        return false;
+    for (uint64_t i = 0; i < n; i++) {
         if (kinds[i] > 1)
             return false;
         if (kinds[i] == 0 && val_offs[i + 1] != val_offs[i] && !values)

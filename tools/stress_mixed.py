@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Mixed-operation GPU stress: randomized interleavings of every C-ABI
 entry point on one handle — writes, batched writes (rrdb_write_batch, which
-the oracle replays through put/remove), flushes, point/range/batched reads with
+the oracle replays through put/remove), batched counter increments
+(rrdb_incr_batch, which the oracle replays through get/ttl/put), flushes, point/range/batched reads with
 the serving lanes forced on, pipelined count scans, paged scans, real
 compactions, checkpoints and restores — cross-checked against the CPU
 oracle driven with the same operation stream.  Complements tools/soak.py
@@ -9,6 +10,7 @@ oracle driven with the same operation stream.  Complements tools/soak.py
 
 Usage: python tools/stress_mixed.py [steps=600] [seed=11]
 """
+import ctypes
 import os
 import random
 import sys
@@ -19,6 +21,59 @@ sys.path.insert(0, REPO)
 
 from incubator_pegasus_amd import data as D  # noqa: E402
 from incubator_pegasus_amd.capi import OK, RrdbLib  # noqa: E402
+
+
+_LIBC = ctypes.CDLL(None, use_errno=True)
+_LIBC.strtoll.restype = ctypes.c_longlong
+_LIBC.strtoll.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+
+
+def buf2int64(s):
+    """dsn::buf2int64: strtoll over the whole span, no range error"""
+    buf = ctypes.create_string_buffer(s, len(s) + 1)
+    end = ctypes.c_void_p()
+    ctypes.set_errno(0)
+    v = _LIBC.strtoll(buf, ctypes.byref(end), 0)
+    if not s or end.value - ctypes.addressof(buf) != len(s) or ctypes.get_errno() != 0:
+        return None
+    return v
+
+
+def replay_incr(o, ops, now):
+    """the batch on the oracle: every base read before the first put (an
+    oracle read flushes), then the reference's incr op by op on a shadow of
+    the touched keys, its successful puts, one flush"""
+    assert o.flush() == OK
+    shadow = {}
+    for k in {op[0] for op in ops}:
+        e, val = o.get(k, now)
+        if e == OK:
+            _, ttl = o.ttl(k, now)
+            shadow[k] = (val, now + ttl if ttl > 0 else 0)
+    values, errors = [], []
+    for k, inc, d in ops:
+        old = shadow.get(k)
+        if old is not None and 0 < old[1] <= now:
+            old = None
+        if old is None:
+            new, ne = inc, (d if d > 0 else 0)
+        else:
+            new = inc
+            if old[0]:
+                cur = buf2int64(old[0])
+                new = None if cur is None else cur + inc
+                if new is None or not -2**63 <= new < 2**63:
+                    values.append(0 if cur is None else cur)
+                    errors.append(4)  # kInvalidArgument
+                    continue
+            ne = old[1] if d == 0 else (0 if d < 0 else d)
+        hk, sk = D.restore_key(k)
+        assert o.put(hk, sk, b"%d" % new, ne, now) == OK
+        shadow[k] = (b"%d" % new, ne)
+        values.append(new)
+        errors.append(OK)
+    assert o.flush() == OK
+    return values, errors
 
 
 def main():
@@ -39,8 +94,19 @@ def main():
     tmp_o = tempfile.mkdtemp(prefix="stress_ckpt_o_")
     decree = 0
     for step in range(steps):
-        op = rnd.randrange(11)
-        if op == 10:  # batched write: the engine sorts and dedups it on the
+        op = rnd.randrange(12)
+        if op == 11:  # batched increments: most stored values are no integers
+            # (the op fails and writes nothing) until an incr has replaced them
+            ops = [(D.generate_key(b"hk%03d" % rnd.randrange(70), b"s%02d" % rnd.randrange(7)),
+                    rnd.choice([1, -1, 5, 2**62, -2**62]),
+                    rnd.choice([0, 0, 0, -1, now + 50, now - 1]))
+                   for _ in range(rnd.choice([1, 7, 300, 2049, 5000]))]
+            err, values, errors, st = g.incr_batch(ops, now)
+            assert err == OK and st.input_ops == len(ops)
+            assert (values, errors) == replay_incr(o, ops, now)
+            assert g.num_runs() == o.num_runs() and g.num_records() == o.num_records()
+            checks += 1
+        elif op == 10:  # batched write: the engine sorts and dedups it on the
             # device; the oracle takes the same ops one by one.  The batch
             # flushes the memtable ahead of itself and ends in a run of its
             # own, so the oracle flushes at those two points
