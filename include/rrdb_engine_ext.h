@@ -151,6 +151,81 @@
  *     time).  Env "engine.incr_lane_max" (default 32) is the longest chain one
  *     lane walks; a longer one is scanned by a whole wave.
  *
+ * Batched check-and-mutate.  The read-modify-write family ends with the
+ * compare-and-swap pair check_and_set / check_and_mutate
+ * (pegasus_write_service_impl.h:436-530, :710-833); check_and_set is
+ * check_and_mutate with a one-PUT mutate list, so one call covers both.
+ * rrdb_check_and_mutate_batch takes n such ops unsorted, in commit order,
+ * duplicate keys allowed, and checks and applies them on the device.  The call
+ * leaves behind exactly what this sequence leaves behind, ending in at most
+ * one new run: flush the memtable; for i = 0..n-1 apply op i as the reference
+ * does (its own read of the check key and, when the check passes, its own
+ * rrdb_put / rrdb_remove per mutation, in list order); rrdb_flush.
+ *   - An op is a check key (a full key [u16 BE hklen][hashkey][sortkey], as
+ *     rrdb_get takes it), a check_type (int32, numbered as cas_check_type in
+ *     idl/rrdb.thrift: 0 = CT_NO_CHECK ... 17 = CT_VALUE_INT_GREATER), a check
+ *     operand (a byte span) and a list of mutations.  The lists of all ops are
+ *     stored together and the n + 1 offsets mut_offs mark where each op's list
+ *     starts and ends.  A mutation is a full key, a kind (RRDB_KIND_PUT /
+ *     RRDB_KIND_DELETE) and, for a PUT, user data and a uint32 expire_ts.
+ *     check_and_set is one PUT mutation; set_diff_sort_key == false means the
+ *     mutation key equals the check key.  Every mutation key of an op must
+ *     carry the check key's hashkey (the reference builds them all from one
+ *     hash_key); that is validated for the whole batch, and it is what makes
+ *     hashkeys independent of each other on the device.
+ *   - Per op, with `old` the newest version of the check key at that moment,
+ *     earlier ops of this batch included:
+ *       malformed (an empty mutation list, a kind other than 0/1, a check_type
+ *         outside 0..17): errors[i] = kInvalidArgument, no read happens
+ *         (check_exist[i] = 0, the returned check value is empty), nothing is
+ *         written;
+ *       value_exist = `old` is a PUT that is not expired (expire > 0 &&
+ *         expire <= epoch_now is expired); the check value is its user data,
+ *         header stripped.  A PUT that an earlier op of the batch stored with
+ *         an expire_ts already past is "not exist", as rrdb_get reports it;
+ *       the check is the reference's validate_check (:1144-1270): types 0-4
+ *         are the existence checks; 5-7 match anywhere / prefix / postfix (the
+ *         value must exist, an empty operand passes, an operand longer than
+ *         the value fails); 8-12 compare bytes (the value must exist; memcmp
+ *         over the common length, then the shorter one is smaller); 13-17
+ *         compare integers (the value must exist; value and operand both go
+ *         through dsn::buf2int64, the parse described under rrdb_incr_batch,
+ *         and if either does not parse the check fails with invalid_argument);
+ *       passed: every mutation of the list is applied in order, a PUT as
+ *         rrdb_put(key, data, expire_ts, epoch_now) encodes it (the header of
+ *         the handle's pegasus.data_version, timetag 0, and expire_ts == 0
+ *         with a default_ttl env becomes epoch_now + default_ttl), a DELETE as
+ *         rrdb_remove encodes it (a tombstone with an empty value);
+ *         errors[i] = kOk;
+ *       not passed: nothing is written; errors[i] = kInvalidArgument when
+ *         invalid_argument is set, else kTryAgain (RRDB_TRY_AGAIN);
+ *       check_exist[i] = value_exist; when return_check_value[i] is set and
+ *         the value exists, the check value is returned.
+ *   - Only applied mutations consume sequence numbers: the k-th applied
+ *     mutation (op order, then list order) gets next_seq_floor + k and the
+ *     floor advances by mutations_applied.  Per key only the last applied
+ *     mutation is stored.  If nothing is applied no run is added and the floor
+ *     stays; the call still returns kOk.
+ *   - Pending memtable entries are older than the batch: they are flushed
+ *     first into a run of their own, and a failure of that flush is returned.
+ *   - Everything is validated before anything changes.  kInvalidArgument with
+ *     the handle as before: any offsets array that does not start at 0 or
+ *     decreases; mut_offs[n] != the mutation count M (the C call carries no
+ *     separate count: the mutation arrays are read as mut_offs[n] entries,
+ *     and the Python binding refuses arrays of another length); a key
+ *     shorter than 2 bytes; hklen > klen - 2 or hklen == 0xFFFF; a mutation
+ *     key whose [hklen][hashkey] prefix differs from its op's check key;
+ *     n + M > 2^31 - 1 (n is bounded before any array is read, n + M once
+ *     mut_offs is); a required array that is NULL; a split compaction or a
+ *     pipelined count scan pending.  n_ops == 0 is kOk and does nothing.
+ *   - Every allocation proportional to the batch may fail cleanly: on a full
+ *     device the call returns kIOError, no run is added, the floor is
+ *     unchanged, the outputs are unspecified, and a memtable flush that
+ *     already happened stays.
+ *   - rrdb_phase_ms reports cas_sort (sort, heads, hashkey groups),
+ *     cas_lookup, cas_apply (walk and ranks), cas_emit (the run and the
+ *     returned check values) and cas_total (device time).
+ *
  * Compaction route.  One compaction pass is a rank kernel followed by an emit
  * kernel, and which pair runs is decided per pass: from the envs
  * "engine.rank_mode" and "engine.emit_mode", the run count, the key shape of
@@ -280,6 +355,40 @@ int32_t rrdb_incr_batch(void *h, uint64_t n_ops,
                         uint32_t epoch_now,
                         int64_t *new_values, int32_t *errors,
                         rrdb_incr_batch_stats *stats);
+
+enum { RRDB_TRY_AGAIN = 13 }; /* rocksdb::Status::kTryAgain: the check did not pass */
+
+typedef struct {
+    uint64_t input_ops;         /* n_ops                                          */
+    uint64_t passed;            /* errors[i] == kOk                               */
+    uint64_t failed_check;      /* errors[i] == kTryAgain                         */
+    uint64_t failed_invalid;    /* an int check whose value or operand is no int  */
+    uint64_t malformed;         /* empty list, bad kind or bad check_type         */
+    uint64_t mutations_applied; /* sequence numbers consumed                      */
+    uint64_t output_records;    /* records in the new run = distinct keys applied to */
+    uint64_t puts, removes;     /* among the output records                       */
+    uint64_t key_bytes, value_bytes; /* of the new run (values encoded)           */
+} rrdb_cas_batch_stats;
+
+/* Check and apply n_ops check-and-mutate ops, given unsorted in commit order
+ * with duplicate keys allowed, on the device; see the header comment.
+ * check_keys / check_key_offs: full rocksdb keys, packed, n+1 offsets.
+ * check_types[n].  operands / operand_offs: packed, n+1 offsets.  mut_offs:
+ * n+1 offsets into the mutation arrays, mut_offs[n] = M.  mut_keys /
+ * mut_key_offs and mut_values / mut_val_offs: packed, M+1 offsets (a DELETE's
+ * value span is ignored).  mut_expire_ts[M] may be null (all zero).
+ * mut_kinds[M].  return_check_value[n] may be null (none).  errors[n] /
+ * check_exist[n]: caller-owned, either may be null.  check_values may be null;
+ * else count = n and values[i] is op i's check value (len 0 when not asked
+ * for or not existing), freed with rrdb_free_result. */
+int32_t rrdb_check_and_mutate_batch(
+    void *h, uint64_t n_ops, const uint8_t *check_keys, const uint64_t *check_key_offs,
+    const int32_t *check_types, const uint8_t *operands, const uint64_t *operand_offs,
+    const uint64_t *mut_offs, const uint8_t *mut_keys, const uint64_t *mut_key_offs,
+    const uint8_t *mut_values, const uint64_t *mut_val_offs, const uint32_t *mut_expire_ts,
+    const uint8_t *mut_kinds, const uint8_t *return_check_value, uint32_t epoch_now,
+    int32_t *errors, uint8_t *check_exist, rrdb_result *check_values,
+    rrdb_cas_batch_stats *stats);
 
 enum {
     RRDB_ROUTE_NONE = -1,

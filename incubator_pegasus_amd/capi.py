@@ -20,6 +20,7 @@ NOT_FOUND = 1
 CORRUPTION = 2
 INVALID_ARGUMENT = 4
 INCOMPLETE = 7
+TRY_AGAIN = 13  # a check_and_mutate / check_and_set whose check did not pass
 
 # filter types (idl/rrdb.thrift:27-33)
 FT_NO_FILTER = 0
@@ -156,6 +157,22 @@ class _IncrBatchStats(C.Structure):
     ]
 
 
+class _CasBatchStats(C.Structure):
+    _fields_ = [
+        ("input_ops", C.c_uint64),
+        ("passed", C.c_uint64),
+        ("failed_check", C.c_uint64),
+        ("failed_invalid", C.c_uint64),
+        ("malformed", C.c_uint64),
+        ("mutations_applied", C.c_uint64),
+        ("output_records", C.c_uint64),
+        ("puts", C.c_uint64),
+        ("removes", C.c_uint64),
+        ("key_bytes", C.c_uint64),
+        ("value_bytes", C.c_uint64),
+    ]
+
+
 class _CompactRoute(C.Structure):
     _fields_ = [("rank", C.c_int32), ("emit", C.c_int32)]
 
@@ -175,6 +192,31 @@ class IncrBatchStats:
     output_records: int = 0
     key_bytes: int = 0
     value_bytes: int = 0
+
+
+@dataclass
+class CasBatchStats:
+    input_ops: int = 0
+    passed: int = 0
+    failed_check: int = 0
+    failed_invalid: int = 0
+    malformed: int = 0
+    mutations_applied: int = 0
+    output_records: int = 0
+    puts: int = 0
+    removes: int = 0
+    key_bytes: int = 0
+    value_bytes: int = 0
+
+
+# cas_check_type (idl/rrdb.thrift), the check_type of a check_and_mutate op
+CT_NO_CHECK, CT_VALUE_NOT_EXIST, CT_VALUE_NOT_EXIST_OR_EMPTY, CT_VALUE_EXIST, \
+    CT_VALUE_NOT_EMPTY = 0, 1, 2, 3, 4
+CT_VALUE_MATCH_ANYWHERE, CT_VALUE_MATCH_PREFIX, CT_VALUE_MATCH_POSTFIX = 5, 6, 7
+CT_VALUE_BYTES_LESS, CT_VALUE_BYTES_LESS_OR_EQUAL, CT_VALUE_BYTES_EQUAL, \
+    CT_VALUE_BYTES_GREATER_OR_EQUAL, CT_VALUE_BYTES_GREATER = 8, 9, 10, 11, 12
+CT_VALUE_INT_LESS, CT_VALUE_INT_LESS_OR_EQUAL, CT_VALUE_INT_EQUAL, \
+    CT_VALUE_INT_GREATER_OR_EQUAL, CT_VALUE_INT_GREATER = 13, 14, 15, 16, 17
 
 
 def _cslice(b: bytes, keep: list) -> _CSlice:
@@ -340,6 +382,13 @@ class RrdbLib:
             L.rrdb_incr_batch.argtypes = [
                 C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                 C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(_IncrBatchStats)]
+        self.has_check_and_mutate_batch = hasattr(L, "rrdb_check_and_mutate_batch")
+        if self.has_check_and_mutate_batch:
+            L.rrdb_check_and_mutate_batch.restype = C.c_int32
+            L.rrdb_check_and_mutate_batch.argtypes = (
+                [C.c_void_p, C.c_uint64] + [C.c_void_p] * 13 +
+                [C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(_Result),
+                 C.POINTER(_CasBatchStats)])
         self.has_compact_route = hasattr(L, "rrdb_last_compact_route")
         if self.has_compact_route:
             L.rrdb_last_compact_route.restype = C.c_int32
@@ -848,3 +897,113 @@ class RrdbPartition:
         expire = np.array([o[2] for o in ops], dtype=np.int32)
         err, nv, er, stats = self.incr_batch_arrays(keys, koffs, inc, expire, epoch_now)
         return err, [int(x) for x in nv], [int(x) for x in er], stats
+
+    # ---- batched check-and-mutate: engine-only (include/rrdb_engine_ext.h) ----
+    def _need_check_and_mutate_batch(self):
+        if not self.lib.has_check_and_mutate_batch:
+            raise RuntimeError(
+                f"check_and_mutate_batch: backend {self.lib.backend!r} ({self.lib.path}) does "
+                "not export rrdb_check_and_mutate_batch (engine-only extension)")
+
+    def check_and_mutate_batch_arrays(self, check_keys_u8, check_key_offs_u64, check_types_i32,
+                                      operands_u8, operand_offs_u64, mut_offs_u64, mut_keys_u8,
+                                      mut_key_offs_u64, mut_vals_u8, mut_val_offs_u64,
+                                      mut_expire_u32, mut_kinds_u8, return_u8,
+                                      epoch_now: int = 0, *, want_errors=True,
+                                      want_exist=True, want_values=True, want_stats=True):
+        """check_and_mutate_batch from packed numpy arrays (no python loop; the
+        bench and the rejection tests, which hand in malformed arrays, use
+        it).  Any array may be None (passed as NULL); mut_expire_u32 = None
+        means every expire_ts is 0 and return_u8 = None means no check value
+        is asked for.  The want_* switches pass NULL for that output.  The C
+        call takes the mutation count from mut_offs[n]; a mut_offs[n] that
+        differs from len(mut_kinds_u8) is refused here as kInvalidArgument.
+        Returns (err, errors int32 array, check_exist uint8 array,
+        check_values list[bytes], CasBatchStats); an output that was not asked
+        for is None."""
+        import numpy as np
+
+        self._need_check_and_mutate_batch()
+        for a, dt in ((check_keys_u8, np.uint8), (check_key_offs_u64, np.uint64),
+                      (check_types_i32, np.int32), (operands_u8, np.uint8),
+                      (operand_offs_u64, np.uint64), (mut_offs_u64, np.uint64),
+                      (mut_keys_u8, np.uint8), (mut_key_offs_u64, np.uint64),
+                      (mut_vals_u8, np.uint8), (mut_val_offs_u64, np.uint64),
+                      (mut_expire_u32, np.uint32), (mut_kinds_u8, np.uint8),
+                      (return_u8, np.uint8)):
+            assert a is None or (a.dtype == dt and a.flags["C_CONTIGUOUS"]), (a.dtype, dt)
+        n = next(len(a) - d for a, d in ((check_types_i32, 0), (check_key_offs_u64, 1),
+                                         (operand_offs_u64, 1), (mut_offs_u64, 1))
+                 if a is not None)
+        if (mut_offs_u64 is not None and mut_kinds_u8 is not None
+                and len(mut_offs_u64) == n + 1 and int(mut_offs_u64[n]) != len(mut_kinds_u8)):
+            return INVALID_ARGUMENT, None, None, None, CasBatchStats()
+
+        def ptr(a):
+            return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+        errors = np.zeros(n, dtype=np.int32) if want_errors else None
+        exist = np.zeros(n, dtype=np.uint8) if want_exist else None
+        res = _Result() if want_values else None
+        st = _CasBatchStats() if want_stats else None
+        err = self._L.rrdb_check_and_mutate_batch(
+            self._h, n, ptr(check_keys_u8), ptr(check_key_offs_u64), ptr(check_types_i32),
+            ptr(operands_u8), ptr(operand_offs_u64), ptr(mut_offs_u64), ptr(mut_keys_u8),
+            ptr(mut_key_offs_u64), ptr(mut_vals_u8), ptr(mut_val_offs_u64), ptr(mut_expire_u32),
+            ptr(mut_kinds_u8), ptr(return_u8), epoch_now, ptr(errors), ptr(exist),
+            C.byref(res) if res is not None else None, C.byref(st) if st is not None else None)
+        values = None
+        if res is not None:
+            try:
+                if err == OK and res.count:
+                    values = [_read_slice(res.values[i]) for i in range(res.count)]
+                elif err == OK:
+                    values = []
+            finally:
+                self._L.rrdb_free_result(C.byref(res))
+        stats = None if st is None else CasBatchStats(
+            **{f[0]: getattr(st, f[0]) for f in _CasBatchStats._fields_})
+        return err, errors, exist, values, stats
+
+    @staticmethod
+    def pack_check_and_mutate_ops(ops):
+        """ops -> the thirteen input arrays of check_and_mutate_batch_arrays."""
+        import numpy as np
+
+        ck, ckoffs = _pack([o[0] for o in ops])
+        types = np.array([o[1] for o in ops], dtype=np.int32)
+        opd, opoffs = _pack([o[2] for o in ops])
+        muts = [m for o in ops for m in o[3]]
+        moffs = np.zeros(len(ops) + 1, dtype=np.uint64)
+        moffs[1:] = np.cumsum([len(o[3]) for o in ops], dtype=np.uint64)
+        mk, mkoffs = _pack([m[0] for m in muts])
+        mv, mvoffs = _pack([m[1] if m[1] is not None else b"" for m in muts])
+        mexp = np.array([m[2] if m[1] is not None else 0 for m in muts], dtype=np.uint32)
+        kinds = np.array([(m[3] if len(m) > 3 else (0 if m[1] is not None else 1))
+                          for m in muts], dtype=np.uint8)
+        ret = np.array([1 if o[4] else 0 for o in ops], dtype=np.uint8)
+        return ck, ckoffs, types, opd, opoffs, moffs, mk, mkoffs, mv, mvoffs, mexp, kinds, ret
+
+    def check_and_mutate_batch(self, ops, epoch_now: int = 0):
+        """Check and apply `ops`, a list of (check_key, check_type, operand,
+        [(key, value_or_None, expire_ts), ...], return_check_value) in commit
+        order (None = remove; duplicate keys allowed: each op sees the ones
+        before it), as the reference's check_and_mutate would, one after the
+        other, on the device.  A mutation may carry a fourth element, its raw
+        kind byte.  Returns (err, errors, check_exist, check_values,
+        CasBatchStats) with the per-op results as python lists."""
+        self._need_check_and_mutate_batch()
+        if not ops:
+            return OK, [], [], [], CasBatchStats()
+        err, er, ex, vals, stats = self.check_and_mutate_batch_arrays(
+            *self.pack_check_and_mutate_ops(ops), epoch_now)
+        if err != OK:
+            return err, None, None, None, stats
+        return err, [int(x) for x in er], [bool(x) for x in ex], vals, stats
+
+    def check_and_set_batch(self, ops, epoch_now: int = 0):
+        """check_and_set: `ops` is a list of (check_key, check_type, operand,
+        set_key, set_value, set_expire_ts, return_check_value); set_key equal
+        to check_key is set_diff_sort_key == false.  One PUT mutation per op."""
+        return self.check_and_mutate_batch(
+            [(o[0], o[1], o[2], [(o[3], o[4], o[5])], o[6]) for o in ops], epoch_now)

@@ -28,6 +28,7 @@
 #include "../../include/rrdb_engine_ext.h"
 #include "engine_common.h"
 #include "wb_stage.h"
+#include "cas_stage.h"
 
 /* ---- launchers (kernels.hip) ---- */
 void launch_crc64_table_init(const uint64_t *host_table);
@@ -151,6 +152,17 @@ void launch_incr_emit(const IncrArgs &, uint64_t, const uint64_t *, const uint64
                       const uint64_t *, const uint64_t *, uint64_t, uint64_t, uint64_t, uint64_t,
                       uint64_t, uint64_t, uint64_t *, uint64_t *, uint64_t *, uint64_t *,
                       uint8_t *, hipStream_t);
+void launch_cas_heads(const WbKeys &, uint64_t, const uint64_t *, const uint32_t *, uint8_t *,
+                      uint64_t *, uint32_t *, uint64_t *, hipStream_t);
+void launch_cas_group_words(uint64_t, uint64_t, const uint64_t *, const uint32_t *,
+                            const uint64_t *, const uint64_t *, uint8_t *, uint64_t *,
+                            hipStream_t);
+void launch_cas_segs(uint64_t, const uint8_t *, const uint32_t *, uint64_t *, hipStream_t);
+void launch_cas_walk(const CasArgs &, hipStream_t);
+void launch_cas_rows(const CasArgs &, uint64_t *, uint64_t *, uint64_t *, hipStream_t);
+void launch_cas_emit(const CasArgs &, const uint64_t *, const uint64_t *, const uint64_t *,
+                     const uint64_t *, const uint64_t *, uint64_t, uint64_t, uint64_t, uint64_t,
+                     uint64_t *, uint64_t *, uint64_t *, uint64_t *, uint64_t *, hipStream_t);
 
 #define HIP_OK(x)                                                                                 \
     do {                                                                                           \
@@ -4400,6 +4412,354 @@ int32_t rrdb_incr_batch(void *h, uint64_t n_ops, const uint8_t *keys, const uint
     e->runs.push_back(r);
     e->runs_changed();
     e->next_seq_floor += red[IR_APPLIED];
+    results_out();
+    return RRDB_OK;
+}
+
+/* ---- batched check-and-mutate (rrdb_check_and_mutate_batch,
+ * rrdb_engine_ext.h) ----
+ * The host validates and stages the entry columns (cas_stage.h) into one
+ * block that mirrors the front of the device slab and uploads it in one copy
+ * (the arrays the kernels read verbatim go up from the caller's memory);
+ * the device sorts, groups by hashkey, looks the check keys up, walks the ops
+ * and emits the run (kernels.hip, "cas batch").  Two read-backs: the totals
+ * before the run and the result arena are allocated, the per-op results at
+ * the end. */
+static_assert(CAS_ERR_INVALID == RRDB_INVALID_ARGUMENT && CAS_ERR_TRY_AGAIN == RRDB_TRY_AGAIN,
+              "the walk kernel writes these codes");
+int32_t rrdb_check_and_mutate_batch(
+    void *h, uint64_t n_ops, const uint8_t *check_keys, const uint64_t *check_key_offs,
+    const int32_t *check_types, const uint8_t *operands, const uint64_t *operand_offs,
+    const uint64_t *mut_offs, const uint8_t *mut_keys, const uint64_t *mut_key_offs,
+    const uint8_t *mut_values, const uint64_t *mut_val_offs, const uint32_t *mut_expire_ts,
+    const uint8_t *mut_kinds, const uint8_t *return_check_value, uint32_t epoch_now,
+    int32_t *errors, uint8_t *check_exist, rrdb_result *check_values,
+    rrdb_cas_batch_stats *stats)
+{
+    if (stats)
+        *stats = rrdb_cas_batch_stats{};
+    if (check_values)
+        memset(check_values, 0, sizeof(*check_values));
+    if (!h)
+        return RRDB_INVALID_ARGUMENT;
+    auto *e = (HipEngine *)h;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (n_ops == 0)
+        return RRDB_OK;
+    if (e->pend.active || e->pend_scan.active)
+        return RRDB_INVALID_ARGUMENT;
+    uint64_t M = 0, sv_bytes = 0;
+    if (!cas_validate(n_ops, check_keys, check_key_offs, check_types, operands, operand_offs,
+                      mut_offs, mut_keys, mut_key_offs, mut_values, mut_val_offs, mut_kinds, &M) ||
+        !wb_staged_bytes(M, mut_val_offs, mut_kinds, e->data_version, &sv_bytes))
+        return RRDB_INVALID_ARGUMENT;
+    const uint64_t n = n_ops, E = n + M;
+
+    /* pending memtable entries are older than the batch: their own run first */
+    e->activate();
+    int32_t rc = engine_flush(e);
+    if (rc != RRDB_OK)
+        return rc;
+
+    /* one try allocation for everything proportional to n + M; the columns
+     * the host stages come first, so that they go up in one copy */
+    const uint64_t ck_bytes = check_key_offs[n], mk_bytes = mut_key_offs[M];
+    const uint64_t ek_bytes = ck_bytes + mk_bytes, op_bytes = operand_offs[n];
+    const int R = (int)e->runs.size();
+    IncrSlab b;
+    uint8_t *d_ekeys = nullptr, *d_evals = nullptr, *d_ekind = nullptr, *d_opfl = nullptr,
+            *d_ckeys = nullptr, *d_opd = nullptr, *d_khead = nullptr, *d_words = nullptr,
+            *d_exist = nullptr;
+    uint64_t *d_ekoff = nullptr, *d_evoff = nullptr, *d_ckoff = nullptr, *d_opoff = nullptr,
+             *d_moff = nullptr, *d_w0 = nullptr, *d_w1 = nullptr, *d_hhead = nullptr,
+             *d_hrank = nullptr, *d_gw0 = nullptr, *d_gw1 = nullptr, *d_seg_start = nullptr,
+             *d_psc = nullptr, *d_hit = nullptr, *d_ulen = nullptr, *d_applied = nullptr,
+             *d_arank = nullptr, *d_cv_src = nullptr, *d_cv_len = nullptr, *d_cv_off = nullptr,
+             *d_row = nullptr, *d_orank = nullptr, *d_ksz = nullptr, *d_vsz = nullptr,
+             *d_kpos = nullptr, *d_vpos = nullptr, *d_row_ksrc = nullptr, *d_row_vsrc = nullptr,
+             *d_kanch = nullptr, *d_vanch = nullptr, *d_red = nullptr;
+    uint32_t *d_lcp = nullptr, *d_i0 = nullptr, *d_i1 = nullptr, *d_pos = nullptr,
+             *d_glcp = nullptr, *d_gi0 = nullptr, *d_gi1 = nullptr, *d_expire = nullptr,
+             *d_eff = nullptr;
+    int32_t *d_ct = nullptr, *d_status = nullptr, *d_err = nullptr;
+    uint64_t up_bytes = 0;
+    for (int pass = 0; pass < 2; pass++) { /* 0 sizes the slab, 1 hands the pieces out */
+        b.take(&d_ekeys, ek_bytes);
+        b.take(&d_ekoff, (E + 1) * 8);
+        b.take(&d_evals, sv_bytes);
+        b.take(&d_evoff, (E + 1) * 8);
+        b.take(&d_ekind, E);
+        b.take(&d_opfl, n);
+        up_bytes = b.used; /* the end of the staged front */
+        b.take(&d_ckeys, ck_bytes);
+        b.take(&d_ckoff, (n + 1) * 8);
+        b.take(&d_opd, op_bytes);
+        b.take(&d_opoff, (n + 1) * 8);
+        b.take(&d_ct, n * 4);
+        b.take(&d_moff, (n + 1) * 8);
+        b.take(&d_lcp, 256);
+        b.take(&d_w0, E * 8);
+        b.take(&d_w1, E * 8);
+        b.take(&d_i0, E * 4);
+        b.take(&d_i1, E * 4);
+        b.take(&d_khead, E);
+        b.take(&d_hhead, E * 8);
+        b.take(&d_hrank, E * 8);
+        b.take(&d_pos, E * 4);
+        b.take(&d_words, n * 8);
+        b.take(&d_glcp, 256);
+        b.take(&d_gw0, n * 8);
+        b.take(&d_gw1, n * 8);
+        b.take(&d_gi0, n * 4);
+        b.take(&d_gi1, n * 4);
+        b.take(&d_seg_start, (n + 1) * 8);
+        b.take(&d_psc, psum_scratch_elems(E) * 8);
+        if (R) {
+            b.take(&d_status, n * 4);
+            b.take(&d_hit, n * 8);
+            b.take(&d_ulen, n * 8);
+            b.take(&d_expire, n * 4);
+        }
+        b.take(&d_eff, E * 4);
+        b.take(&d_applied, E * 8);
+        b.take(&d_arank, E * 8);
+        b.take(&d_err, n * 4);
+        b.take(&d_exist, n);
+        b.take(&d_cv_src, n * 8);
+        b.take(&d_cv_len, n * 8);
+        b.take(&d_cv_off, (n + 1) * 8);
+        b.take(&d_row, E * 8);
+        b.take(&d_orank, E * 8);
+        b.take(&d_ksz, E * 8);
+        b.take(&d_vsz, E * 8);
+        b.take(&d_kpos, E * 8);
+        b.take(&d_vpos, E * 8);
+        b.take(&d_row_ksrc, M * 8);
+        b.take(&d_row_vsrc, M * 8);
+        b.take(&d_kanch, (((mk_bytes + 15) >> 10) + 2) * 8);
+        b.take(&d_vanch, (((sv_bytes + 15) >> 10) + 2) * 8);
+        b.take(&d_red, CR_WORDS * 8);
+        if (pass == 0 && !b.commit())
+            return RRDB_IO_ERROR;
+    }
+    WbBufs hb; /* host blocks of this call */
+    uint8_t *h_up = hb.get_host<uint8_t>(up_bytes);
+    if (!hb.ok)
+        return RRDB_IO_ERROR;
+    auto host_of = [&](const void *d) { return h_up + ((const uint8_t *)d - b.base); };
+    uint64_t *h_ekoff = (uint64_t *)host_of(d_ekoff);
+    cas_stage(n, check_keys, check_key_offs, check_types, mut_offs, mut_keys, mut_key_offs,
+              mut_values, mut_val_offs, mut_expire_ts, mut_kinds, return_check_value,
+              e->data_version, e->default_ttl, epoch_now, host_of(d_ekeys), h_ekoff,
+              host_of(d_evals), (uint64_t *)host_of(d_evoff), host_of(d_ekind), host_of(d_opfl));
+    const uint64_t in_fk = wb_fixed_stride(h_ekoff, E);
+    b.upload(b.base, h_up, up_bytes);
+    /* what the kernels read as the caller wrote it goes up from where it is */
+    b.upload(d_ckeys, check_keys, ck_bytes);
+    b.upload(d_ckoff, check_key_offs, (n + 1) * 8);
+    b.upload(d_opd, operands, op_bytes);
+    b.upload(d_opoff, operand_offs, (n + 1) * 8);
+    b.upload(d_ct, check_types, n * 4);
+    b.upload(d_moff, mut_offs, (n + 1) * 8);
+    if (b.ok && (hipMemset(d_eff, 0xFF, E * 4) != hipSuccess ||
+                 hipMemset(d_applied, 0, E * 8) != hipSuccess)) {
+        (void)hipGetLastError();
+        b.ok = false;
+    }
+    if (!b.ok)
+        return RRDB_IO_ERROR;
+
+    hipEvent_t ev[6];
+    for (auto &x : ev)
+        HIP_OK(hipEventCreate(&x));
+    auto drop_events = [&] {
+        for (auto &x : ev)
+            (void)hipEventDestroy(x);
+    };
+    /* sort the entries; key heads, hashkey groups, the ops by group */
+    const WbKeys wk{d_ekeys, in_fk ? nullptr : d_ekoff, in_fk, d_lcp};
+    HIP_OK(hipEventRecord(ev[0], e->stream));
+    const int cur = launch_wb_sort(wk, E, d_lcp, d_w0, d_i0, d_w1, d_i1, e->stream);
+    const uint64_t *d_w = cur ? d_w1 : d_w0;
+    const uint32_t *d_ix = cur ? d_i1 : d_i0;
+    launch_cas_heads(wk, E, d_w, d_ix, d_khead, d_hhead, d_pos, d_red, e->stream);
+    launch_psum(d_hhead, d_hrank, E, d_psc, e->stream);
+    launch_cas_group_words(n, E, d_moff, d_pos, d_hhead, d_hrank, d_words, d_red, e->stream);
+    const WbKeys gk{d_words, nullptr, 8, d_glcp};
+    const int gcur = launch_wb_sort(gk, n, d_glcp, d_gw0, d_gi0, d_gw1, d_gi1, e->stream);
+    const uint32_t *d_ops = gcur ? d_gi1 : d_gi0;
+    launch_cas_segs(n, d_words, d_ops, d_seg_start, e->stream);
+    HIP_OK(hipEventRecord(ev[1], e->stream));
+
+    /* the bases: every check key against the runs as they are now */
+    DevRun *dr = R ? e->dev_runs() : nullptr;
+    if (R)
+        launch_get(dr, R, d_ckeys, d_ckoff, n, epoch_now, e->data_version, d_status, d_hit,
+                   d_ulen, d_expire, e->stream);
+    HIP_OK(hipEventRecord(ev[2], e->stream));
+
+    CasArgs a{};
+    a.k = wk;
+    a.n = n;
+    a.E = E;
+    a.ix = d_ix;
+    a.pos = d_pos;
+    a.khead = d_khead;
+    a.svals = d_evals;
+    a.svoff = d_evoff;
+    a.kind = d_ekind;
+    a.op_flags = d_opfl;
+    a.ctype = d_ct;
+    a.opd = d_opd;
+    a.opoff = d_opoff;
+    a.moff = d_moff;
+    a.ops = d_ops;
+    a.seg_start = d_seg_start;
+    a.status = d_status;
+    a.hit = d_hit;
+    a.runs = dr;
+    a.data_version = e->data_version;
+    a.epoch_now = epoch_now;
+    a.eff = d_eff;
+    a.applied = d_applied;
+    a.err = d_err;
+    a.exist = d_exist;
+    a.cv_src = d_cv_src;
+    a.cv_len = d_cv_len;
+    a.red = (unsigned long long *)d_red;
+    launch_cas_walk(a, e->stream);
+    launch_psum(d_applied, d_arank, E, d_psc, e->stream);
+    launch_cas_rows(a, d_row, d_ksz, d_vsz, e->stream);
+    launch_psum(d_row, d_orank, E, d_psc, e->stream);
+    launch_psum(d_ksz, d_kpos, E, d_psc, e->stream);
+    launch_psum(d_vsz, d_vpos, E, d_psc, e->stream);
+    if (check_values)
+        launch_psum(d_cv_len, d_cv_off, n, d_psc, e->stream);
+    HIP_OK(hipEventRecord(ev[3], e->stream));
+
+    /* the totals: one read */
+    uint64_t red[CR_WORDS];
+    HIP_OK(hipMemcpyAsync(red, d_red, sizeof(red), hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipStreamSynchronize(e->stream));
+    const uint64_t n_out = red[CR_NOUT], kbytes = red[CR_KBYTES], vbytes = red[CR_VBYTES];
+    const uint64_t applied = red[CR_APPLIED], ret_bytes = red[CR_RETBYTES];
+    if (n_out > M || applied > M || kbytes > mk_bytes || vbytes > sv_bytes ||
+        (n_out == 0) != (applied == 0)) {
+        drop_events();
+        return RRDB_IO_ERROR; /* cannot happen: the totals come from the staged columns */
+    }
+
+    /* the returned check values: gathered into one device buffer, then one
+     * copy into the result's arena */
+    HIP_OK(hipEventRecord(ev[4], e->stream));
+    WbBufs cvb;
+    if (check_values) {
+        Arena *ar = result_init(check_values);
+        rrdb_slice *sl = (rrdb_slice *)ar->alloc(n * sizeof(rrdb_slice));
+        uint8_t *blk = (uint8_t *)ar->alloc(ret_bytes);
+        uint64_t *h_len = cvb.get_host<uint64_t>(n * 8);
+        const uint64_t anch_bytes = ((((ret_bytes + 15) >> 10) + 2) * 8 + 255) & ~255ull;
+        uint8_t *d_cv = ret_bytes ? cvb.get<uint8_t>(anch_bytes + ret_bytes) : nullptr;
+        if (!sl || !blk || !cvb.ok) {
+            drop_events();
+            return RRDB_IO_ERROR;
+        }
+        if (ret_bytes) {
+            HIP_OK(hipMemcpyAsync(d_cv_off + n, d_red + CR_RETBYTES, 8, hipMemcpyDeviceToDevice,
+                                  e->stream));
+            launch_split_copy(d_cv_src, d_cv_off, n, 0, ret_bytes, (uint64_t *)d_cv,
+                              d_cv + anch_bytes, e->stream);
+            HIP_OK(hipMemcpyAsync(blk, d_cv + anch_bytes, ret_bytes, hipMemcpyDeviceToHost,
+                                  e->stream));
+        }
+        HIP_OK(hipMemcpyAsync(h_len, d_cv_len, n * 8, hipMemcpyDeviceToHost, e->stream));
+        HIP_OK(hipStreamSynchronize(e->stream));
+        uint64_t at = 0;
+        for (uint64_t i = 0; i < n; i++) {
+            sl[i] = {blk + at, h_len[i]};
+            at += h_len[i];
+        }
+        if (at != ret_bytes) {
+            drop_events();
+            return RRDB_IO_ERROR; /* cannot happen: one column, summed twice */
+        }
+        check_values->values = sl;
+        check_values->count = n;
+        check_values->error = RRDB_OK;
+    }
+
+    auto results_out = [&]() {
+        if (errors)
+            HIP_OK(hipMemcpy(errors, d_err, n * 4, hipMemcpyDeviceToHost));
+        if (check_exist)
+            HIP_OK(hipMemcpy(check_exist, d_exist, n, hipMemcpyDeviceToHost));
+        if (stats) {
+            stats->input_ops = n;
+            stats->passed = red[CR_PASSED];
+            stats->failed_check = red[CR_FCHECK];
+            stats->failed_invalid = red[CR_FINVALID];
+            stats->malformed = red[CR_MALFORMED];
+            stats->mutations_applied = applied;
+            stats->output_records = n_out;
+            stats->puts = red[CR_PUTS];
+            stats->removes = n_out - red[CR_PUTS];
+            stats->key_bytes = kbytes;
+            stats->value_bytes = vbytes;
+        }
+    };
+    auto timers = [&]() {
+        float ms = 0, tot = 0;
+        if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
+            e->phase_ms["cas_sort"] = ms;
+        if (hipEventElapsedTime(&ms, ev[1], ev[2]) == hipSuccess)
+            e->phase_ms["cas_lookup"] = ms;
+        if (hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess)
+            e->phase_ms["cas_apply"] = ms;
+        e->phase_ms["cas_emit"] = 0.0;
+        if (hipEventElapsedTime(&ms, ev[4], ev[5]) == hipSuccess)
+            e->phase_ms["cas_emit"] = ms;
+        if (hipEventElapsedTime(&tot, ev[0], ev[3]) == hipSuccess)
+            e->phase_ms["cas_total"] = tot + e->phase_ms["cas_emit"];
+    };
+    if (n_out == 0) { /* no check passed: no run, the floor stays */
+        HIP_OK(hipEventRecord(ev[5], e->stream));
+        HIP_OK(hipStreamSynchronize(e->stream));
+        timers();
+        drop_events();
+        results_out();
+        return RRDB_OK;
+    }
+
+    RunBuf r;
+    if (!e->alloc_base(r, n_out, kbytes, vbytes, RunAlloc::Try)) {
+        drop_events();
+        return RRDB_IO_ERROR;
+    }
+    /* the strides detect_fixed_* would report for the emitted run */
+    auto u32_or_0 = [](uint64_t v) { return v > UINT32_MAX ? 0u : (uint32_t)v; };
+    r.fixed_klen = red[CR_KMIN] == red[CR_KMAX] ? u32_or_0(red[CR_KMIN]) : 0;
+    r.fixed_vlen = red[CR_VMIN] == red[CR_VMAX] ? u32_or_0(red[CR_VMIN]) : 0;
+    r.fixed_vlen_put =
+        red[CR_PUTS] && red[CR_PVMIN] == red[CR_PVMAX] ? u32_or_0(red[CR_PVMIN]) : 0;
+    launch_cas_emit(a, d_row, d_orank, d_kpos, d_vpos, d_arank, e->next_seq_floor, n_out, kbytes,
+                    vbytes, r.koff, r.voff, r.sk, d_row_ksrc, d_row_vsrc, e->stream);
+    launch_split_copy(d_row_ksrc, r.koff, n_out, r.fixed_klen, kbytes, d_kanch, r.keys,
+                      e->stream);
+    launch_split_copy(d_row_vsrc, r.voff, n_out, r.fixed_vlen, vbytes, d_vanch, r.vals,
+                      e->stream);
+    HIP_OK(hipEventRecord(ev[5], e->stream));
+    if (!e->finish_run(r, nullptr, RunAlloc::Try, e->bloom_enabled)) {
+        e->free_run(r);
+        drop_events();
+        return RRDB_IO_ERROR;
+    }
+    HIP_OK(hipStreamSynchronize(e->stream));
+    timers();
+    drop_events();
+
+    e->runs.push_back(r);
+    e->runs_changed();
+    e->next_seq_floor += applied;
     results_out();
     return RRDB_OK;
 }

@@ -94,6 +94,56 @@ struct IncrArgs {
     unsigned long long *red; /* IR_* */
 };
 
+/* cas batch (rrdb_check_and_mutate_batch) reduction (one block of u64 words,
+ * vector atomics).  CR_NGRP is the number of hashkey groups; CR_PASSED ..
+ * CR_RETBYTES come from the walk, the rest from the output rows. */
+enum {
+    CR_NGRP = 0, CR_PASSED, CR_FCHECK, CR_FINVALID, CR_MALFORMED, CR_APPLIED, CR_RETBYTES,
+    CR_NOUT, CR_PUTS, CR_KBYTES, CR_VBYTES, CR_KMIN, CR_KMAX, CR_VMIN, CR_VMAX, CR_PVMIN,
+    CR_PVMAX, CR_WORDS
+};
+
+#define CAS_NONE 0xFFFFFFFFu
+/* errors[i]: RRDB_INVALID_ARGUMENT / RRDB_TRY_AGAIN (engine.cpp asserts they agree) */
+#define CAS_ERR_INVALID 4
+#define CAS_ERR_TRY_AGAIN 13
+
+/* everything the walk, row and emit kernels of rrdb_check_and_mutate_batch
+ * share, by value.  "entry order" is the staged ordinal (cas_stage.h), a
+ * "position" is an index into the sorted entries (key asc, ordinal desc). */
+struct CasArgs {
+    WbKeys k;               /* the staged entry keys, entry order               */
+    uint64_t n, E;          /* ops, entries                                      */
+    const uint32_t *ix;     /* [E] position -> entry                             */
+    const uint32_t *pos;    /* [E] entry -> position                             */
+    const uint8_t *khead;   /* [E] 1 = the position starts a full key            */
+    const uint8_t *svals;   /* staged values, entry order                        */
+    const uint64_t *svoff;  /* [E+1]                                             */
+    const uint8_t *kind;    /* [E] CAS_ENT_*                                     */
+    const uint8_t *op_flags;  /* [n] CAS_OP_*                                    */
+    const int32_t *ctype;   /* [n]                                               */
+    const uint8_t *opd;     /* check operands                                    */
+    const uint64_t *opoff;  /* [n+1]                                             */
+    const uint64_t *moff;   /* [n+1] mut_offs                                    */
+    const uint32_t *ops;    /* [n] ops by (hashkey group asc, op asc)            */
+    const uint64_t *seg_start; /* [n_grp+1] into ops                             */
+    /* the lookup of every check key against the runs (launch_get), op order;
+     * status null = the handle has no run, every base is absent */
+    const int32_t *status;
+    const uint64_t *hit;
+    const DevRun *runs;
+    uint32_t data_version, epoch_now;
+    /* eff[q]: position of the newest applied mutation at or older than q
+     * within q's key group, CAS_NONE when there is none */
+    uint32_t *eff;
+    uint64_t *applied;      /* [E] entry order, 1 = an applied mutation          */
+    /* per op, op order */
+    int32_t *err;
+    uint8_t *exist;
+    uint64_t *cv_src, *cv_len; /* the returned check value (len 0 = none)        */
+    unsigned long long *red;   /* CR_* */
+};
+
 /* device-visible descriptor of one sorted run */
 struct DevRun {
     const uint8_t *keys;

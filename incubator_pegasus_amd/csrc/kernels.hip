@@ -4436,3 +4436,384 @@ void launch_incr_emit(const IncrArgs &a, uint64_t n_seg, const uint64_t *d_okran
                                                         d_okoff, d_ovoff, d_osk, d_row_ksrc,
                                                         d_ovals);
 }
+
+/* ================= cas batch (rrdb_check_and_mutate_batch) =================
+ * n check-and-mutate ops, unsorted, duplicate keys allowed, applied as the
+ * sequence get + put/remove per op would apply them, ending in one run:
+ *   entries:  op i's check key followed by its mutation keys, E = n + M in
+ *             all, staged by the host in that (ordinal) order (cas_stage.h).
+ *   sort:     launch_wb_sort over the entries: key asc, ordinal desc.  Equal
+ *             keys stand together newest first, and so do equal
+ *             [hklen][hashkey] prefixes.  Head flags per key and per prefix,
+ *             and the inverse permutation pos[entry].
+ *   groups:   launch_psum of the prefix heads numbers the hashkey groups; a
+ *             second launch_wb_sort over 8-byte (group, op) words orders the
+ *             ops by group, oldest first, and every group's first slot is its
+ *             segment start.
+ *   lookup:   launch_get over the n check keys.
+ *   walk:     one lane per hashkey group takes its ops oldest to newest.  A
+ *             mutation key always carries its op's hashkey, so everything an
+ *             op can read or shadow belongs to the same lane.  eff[q] is the
+ *             position of the newest applied mutation at or older than q in
+ *             q's key group: a check at p reads eff[p+1] (the lane's own
+ *             earlier store), falls back to the lookup, and runs cas_check
+ *             (cas_check.h); then the op's entries get their eff in ordinal
+ *             order.
+ *   rank:     launch_psum of "entry is an applied mutation" in ordinal order
+ *             gives the seqnos; a key head with eff != none is an output row.
+ *   emit:     sk / offsets / source addresses by row, then the split's chunk
+ *             copies move key and value bytes; the returned check values go
+ *             through the same copy into one buffer.
+ * Every result is a function of the sorted order alone, so it does not depend
+ * on the grid or on scheduling. */
+#include "cas_check.h"
+#include "cas_stage.h" /* CAS_ENT_*, CAS_OP_* */
+
+/* khead[p] / hhead[p] = 1 iff position p starts a full key / a hashkey group;
+ * pos[] is the inverse of ix[] */
+__global__ void __launch_bounds__(BLOCK)
+    k_cas_heads(WbKeys k, uint64_t E, const uint64_t *w, const uint32_t *ix, uint8_t *khead,
+                uint64_t *hhead, uint32_t *pos)
+{
+    const uint64_t L = *k.lcp;
+    for (uint64_t p = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; p < E;
+         p += gridDim.x * (uint64_t)blockDim.x) {
+        const uint32_t i = ix[p];
+        if (i >= E)
+            continue; /* cannot happen: the sort permutes 0..E-1 */
+        pos[i] = (uint32_t)p;
+        bool kh = true, hh = true;
+        if (p) {
+            const uint32_t j = ix[p - 1];
+            kh = w[p] != w[p - 1] || wb_tail_cmp(k, L, j, i) != 0;
+            hh = false;
+            if (kh) {
+                uint64_t la, lb;
+                const uint8_t *a = wb_key(k, j, &la);
+                const uint8_t *b = wb_key(k, i, &lb);
+                /* validated: both are at least 2 + hklen bytes long */
+                const uint64_t ha = ((uint64_t)a[0] << 8) | a[1], hb = ((uint64_t)b[0] << 8) | b[1];
+                hh = ha != hb || dev_key_cmp(a + 2, ha, b + 2, hb) != 0;
+            }
+        }
+        khead[p] = kh ? 1 : 0;
+        hhead[p] = hh ? 1 : 0;
+    }
+}
+
+/* word[i] = (hashkey group of op i, i), big-endian, the key of the second
+ * sort; red[CR_NGRP] = the number of groups */
+__global__ void __launch_bounds__(BLOCK)
+    k_cas_group_words(uint64_t n, uint64_t E, const uint64_t *moff, const uint32_t *pos,
+                      const uint64_t *hhead, const uint64_t *hrank, uint8_t *words,
+                      unsigned long long *red)
+{
+    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n;
+         i += gridDim.x * (uint64_t)blockDim.x) {
+        if (i == 0)
+            red[CR_NGRP] = hrank[E - 1] + hhead[E - 1];
+        const uint64_t e = i + moff[i];
+        if (e >= E)
+            continue; /* cannot happen: validated offsets */
+        const uint32_t p = pos[e];
+        const uint64_t g = hrank[p] + hhead[p] - 1; /* position 0 is a head */
+        const uint64_t wd = __builtin_bswap64((g << 32) | i);
+        __builtin_memcpy(words + i * 8, &wd, 8);
+    }
+}
+
+/* seg_start[g] = the first slot of group g in the sorted ops, seg_start[G] = n */
+__global__ void __launch_bounds__(BLOCK)
+    k_cas_segs(uint64_t n, const uint8_t *words, const uint32_t *ops, uint64_t *seg_start)
+{
+    for (uint64_t q = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; q < n;
+         q += gridDim.x * (uint64_t)blockDim.x) {
+        uint64_t wa, wb = 0;
+        __builtin_memcpy(&wa, words + (uint64_t)ops[q] * 8, 8);
+        const uint64_t g = __builtin_bswap64(wa) >> 32;
+        if (q) {
+            __builtin_memcpy(&wb, words + (uint64_t)ops[q - 1] * 8, 8);
+            wb = __builtin_bswap64(wb) >> 32;
+        }
+        if (g >= n)
+            continue; /* cannot happen: every group holds an op */
+        if (q == 0 || g != wb)
+            seg_start[g] = q;
+        if (q == n - 1)
+            seg_start[g + 1] = n;
+    }
+}
+
+struct CasTally {
+    unsigned long long passed = 0, fcheck = 0, finvalid = 0, malformed = 0, applied = 0,
+                       retbytes = 0;
+};
+
+/* eff of the position after q when it belongs to q's key group */
+__device__ static inline uint32_t cas_older(const CasArgs &a, uint32_t q)
+{
+    return ((uint64_t)q + 1 < a.E && !a.khead[q + 1]) ? a.eff[q + 1] : CAS_NONE;
+}
+
+/* op i, all older ops of its hashkey resolved: the reference's
+ * check_and_mutate */
+__device__ static void cas_op(const CasArgs &a, uint32_t i, CasTally &t)
+{
+    const uint64_t m0 = a.moff[i], m1 = a.moff[i + 1];
+    const uint64_t e0 = i + m0;
+    if (m1 < m0 || e0 + (m1 - m0) >= a.E)
+        return; /* cannot happen: validated offsets */
+    const uint8_t fl = a.op_flags[i];
+    const uint32_t hdr = dev_hdr_len(a.data_version);
+    bool exist = false, passed = false, invalid = false;
+    const uint8_t *val = nullptr;
+    uint64_t vl = 0;
+    if (!(fl & CAS_OP_MALFORMED)) {
+        const uint32_t b = cas_older(a, a.pos[e0]);
+        if (b == CAS_NONE) { /* no earlier op of the batch wrote the key */
+            if (a.status && a.status[i] == 0) {
+                const uint64_t id = a.hit[i];
+                uint64_t rl;
+                const uint8_t *rv = run_val(a.runs[id >> 40], id & 0xFFFFFFFFFFull, &rl);
+                if (rl >= hdr) {
+                    exist = true;
+                    val = rv + hdr;
+                    vl = rl - hdr;
+                }
+            }
+        } else if (b < a.E) {
+            const uint32_t em = a.ix[b];
+            if (a.kind[em] == CAS_ENT_PUT) {
+                const uint8_t *sv = a.svals + a.svoff[em];
+                const uint64_t sl = a.svoff[em + 1] - a.svoff[em];
+                if (sl >= hdr && !dev_ts_expired(a.epoch_now, dev_expire_ts(a.data_version, sv))) {
+                    exist = true;
+                    val = sv + hdr;
+                    vl = sl - hdr;
+                }
+            }
+        }
+        passed = cas_check(a.ctype[i], exist, val, vl, a.opd + a.opoff[i],
+                           a.opoff[i + 1] - a.opoff[i], &invalid);
+    }
+    if (fl & CAS_OP_MALFORMED) {
+        a.err[i] = CAS_ERR_INVALID;
+        t.malformed++;
+    } else if (passed) {
+        a.err[i] = 0;
+        t.passed++;
+        t.applied += m1 - m0;
+    } else if (invalid) {
+        a.err[i] = CAS_ERR_INVALID;
+        t.finvalid++;
+    } else {
+        a.err[i] = CAS_ERR_TRY_AGAIN;
+        t.fcheck++;
+    }
+    a.exist[i] = exist ? 1 : 0;
+    const bool ret = exist && (fl & CAS_OP_RETURN);
+    a.cv_src[i] = ret ? (uint64_t)val : 0;
+    a.cv_len[i] = ret ? vl : 0;
+    t.retbytes += ret ? vl : 0;
+    /* ascending ordinal = within a key group, descending position: the entry
+     * a store reads from is always written first */
+    for (uint64_t e = e0; e <= e0 + (m1 - m0); e++) {
+        const uint32_t q = a.pos[e];
+        const bool ap = passed && e != e0;
+        a.eff[q] = ap ? q : cas_older(a, q);
+        a.applied[e] = ap ? 1 : 0;
+    }
+}
+
+/* block-level then device-level fold of the per-thread walk tallies */
+__device__ static inline void cas_tally_flush(const CasTally &t, unsigned long long *s_red,
+                                              unsigned long long *red)
+{
+    if (threadIdx.x < CR_WORDS)
+        s_red[threadIdx.x] = 0;
+    __syncthreads();
+    if (t.passed)
+        atomicAdd(&s_red[CR_PASSED], t.passed);
+    if (t.fcheck)
+        atomicAdd(&s_red[CR_FCHECK], t.fcheck);
+    if (t.finvalid)
+        atomicAdd(&s_red[CR_FINVALID], t.finvalid);
+    if (t.malformed)
+        atomicAdd(&s_red[CR_MALFORMED], t.malformed);
+    if (t.applied)
+        atomicAdd(&s_red[CR_APPLIED], t.applied);
+    if (t.retbytes)
+        atomicAdd(&s_red[CR_RETBYTES], t.retbytes);
+    __syncthreads();
+    if (threadIdx.x >= CR_PASSED && threadIdx.x <= CR_RETBYTES && s_red[threadIdx.x])
+        atomicAdd(&red[threadIdx.x], s_red[threadIdx.x]);
+}
+
+/* one lane per hashkey group, its ops oldest to newest */
+__global__ void __launch_bounds__(BLOCK) k_cas_walk_lane(CasArgs a)
+{
+    __shared__ unsigned long long s_red[CR_WORDS];
+    CasTally t;
+    const uint64_t ng = a.red[CR_NGRP];
+    for (uint64_t g = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; g < ng && g < a.n;
+         g += gridDim.x * (uint64_t)blockDim.x) {
+        const uint64_t beg = a.seg_start[g], end = a.seg_start[g + 1];
+        if (end <= beg || end > a.n)
+            continue;
+        for (uint64_t q = beg; q < end; q++) {
+            const uint32_t i = a.ops[q];
+            if (i < a.n)
+                cas_op(a, i, t);
+        }
+    }
+    cas_tally_flush(t, s_red, a.red);
+}
+
+/* the output rows: a key head whose eff is set.  row[p], its key and value
+ * sizes (0 when no row) for the scans, and the row totals into red[CR_*]. */
+__global__ void __launch_bounds__(BLOCK)
+    k_cas_rows(CasArgs a, uint64_t *row, uint64_t *ksz, uint64_t *vsz)
+{
+    __shared__ unsigned long long s_red[CR_WORDS];
+    if (threadIdx.x < CR_WORDS)
+        s_red[threadIdx.x] = (threadIdx.x == CR_KMIN || threadIdx.x == CR_VMIN ||
+                              threadIdx.x == CR_PVMIN)
+                                 ? ~0ull
+                                 : 0ull;
+    __syncthreads();
+    unsigned long long nout = 0, puts = 0, kb = 0, vb = 0, kmin = ~0ull, kmax = 0, vmin = ~0ull,
+                       vmax = 0, pvmin = ~0ull, pvmax = 0;
+    for (uint64_t p = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; p < a.E;
+         p += gridDim.x * (uint64_t)blockDim.x) {
+        const uint32_t q = a.khead[p] ? a.eff[p] : CAS_NONE;
+        uint64_t kl = 0, vl = 0;
+        const bool has = q != CAS_NONE && q < a.E;
+        if (has) {
+            const uint32_t em = a.ix[q];
+            (void)wb_key(a.k, em, &kl);
+            vl = a.svoff[em + 1] - a.svoff[em];
+            nout++;
+            kb += kl;
+            vb += vl;
+            kmin = kl < kmin ? kl : kmin;
+            kmax = kl > kmax ? kl : kmax;
+            vmin = vl < vmin ? vl : vmin;
+            vmax = vl > vmax ? vl : vmax;
+            if (a.kind[em] == CAS_ENT_PUT) {
+                puts++;
+                pvmin = vl < pvmin ? vl : pvmin;
+                pvmax = vl > pvmax ? vl : pvmax;
+            }
+        }
+        row[p] = has ? 1 : 0;
+        ksz[p] = kl;
+        vsz[p] = vl;
+    }
+    if (nout) {
+        atomicAdd(&s_red[CR_NOUT], nout);
+        atomicAdd(&s_red[CR_KBYTES], kb);
+        atomicAdd(&s_red[CR_VBYTES], vb);
+        atomicMin(&s_red[CR_KMIN], kmin);
+        atomicMax(&s_red[CR_KMAX], kmax);
+        atomicMin(&s_red[CR_VMIN], vmin);
+        atomicMax(&s_red[CR_VMAX], vmax);
+        if (puts) {
+            atomicAdd(&s_red[CR_PUTS], puts);
+            atomicMin(&s_red[CR_PVMIN], pvmin);
+            atomicMax(&s_red[CR_PVMAX], pvmax);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x >= CR_NOUT && threadIdx.x < CR_WORDS) {
+        const unsigned long long v = s_red[threadIdx.x];
+        if (threadIdx.x == CR_KMIN || threadIdx.x == CR_VMIN || threadIdx.x == CR_PVMIN)
+            atomicMin(&a.red[threadIdx.x], v);
+        else if (threadIdx.x == CR_KMAX || threadIdx.x == CR_VMAX || threadIdx.x == CR_PVMAX)
+            atomicMax(&a.red[threadIdx.x], v);
+        else if (v)
+            atomicAdd(&a.red[threadIdx.x], v);
+    }
+}
+
+/* the rows, by rank: osk, 0-based okoff/ovoff (n_out+1 entries) and the
+ * per-row source addresses the chunk copies read */
+__global__ void __launch_bounds__(BLOCK)
+    k_cas_emit(CasArgs a, const uint64_t *row, const uint64_t *orank, const uint64_t *kpos,
+               const uint64_t *vpos, const uint64_t *arank, uint64_t seq_floor, uint64_t n_out,
+               uint64_t kbytes, uint64_t vbytes, uint64_t *okoff, uint64_t *ovoff, uint64_t *osk,
+               uint64_t *row_ksrc, uint64_t *row_vsrc)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        okoff[n_out] = kbytes;
+        ovoff[n_out] = vbytes;
+    }
+    for (uint64_t p = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; p < a.E;
+         p += gridDim.x * (uint64_t)blockDim.x) {
+        if (!row[p])
+            continue;
+        const uint64_t r = orank[p];
+        const uint32_t q = a.eff[p];
+        if (r >= n_out || q >= a.E)
+            continue; /* cannot happen: n_out is this scan's total */
+        const uint32_t em = a.ix[q];
+        uint64_t kl;
+        osk[r] = ((seq_floor + arank[em]) << 1) | (uint64_t)(a.kind[em] & 1);
+        okoff[r] = kpos[p];
+        ovoff[r] = vpos[p];
+        row_ksrc[r] = (uint64_t)wb_key(a.k, em, &kl);
+        row_vsrc[r] = (uint64_t)(a.svals + a.svoff[em]);
+    }
+}
+
+/* head flags and the inverse permutation.  d_red: CR_WORDS u64 words,
+ * initialised here. */
+void launch_cas_heads(const WbKeys &k, uint64_t E, const uint64_t *d_w, const uint32_t *d_ix,
+                      uint8_t *d_khead, uint64_t *d_hhead, uint32_t *d_pos, uint64_t *d_red,
+                      hipStream_t s)
+{
+    uint64_t init[CR_WORDS];
+    for (int j = 0; j < CR_WORDS; j++)
+        init[j] = (j == CR_KMIN || j == CR_VMIN || j == CR_PVMIN) ? ~0ull : 0ull;
+    HIP_CHECK(hipMemcpyAsync(d_red, init, sizeof(init), hipMemcpyHostToDevice, s));
+    k_cas_heads<<<grid_for(E, BLOCK), BLOCK, 0, s>>>(k, E, d_w, d_ix, d_khead, d_hhead, d_pos);
+}
+
+/* after the caller's launch_psum of d_hhead into d_hrank: the words the
+ * second sort orders the ops by */
+void launch_cas_group_words(uint64_t n, uint64_t E, const uint64_t *d_moff, const uint32_t *d_pos,
+                            const uint64_t *d_hhead, const uint64_t *d_hrank, uint8_t *d_words,
+                            uint64_t *d_red, hipStream_t s)
+{
+    k_cas_group_words<<<grid_for(n, BLOCK), BLOCK, 0, s>>>(n, E, d_moff, d_pos, d_hhead, d_hrank,
+                                                          d_words, (unsigned long long *)d_red);
+}
+
+void launch_cas_segs(uint64_t n, const uint8_t *d_words, const uint32_t *d_ops,
+                     uint64_t *d_seg_start, hipStream_t s)
+{
+    k_cas_segs<<<grid_for(n, BLOCK), BLOCK, 0, s>>>(n, d_words, d_ops, d_seg_start);
+}
+
+/* the group count is read on the device, so the grid is sized by the op
+ * count, which bounds it */
+void launch_cas_walk(const CasArgs &a, hipStream_t s)
+{
+    k_cas_walk_lane<<<grid_for(a.n, BLOCK), BLOCK, 0, s>>>(a);
+}
+
+void launch_cas_rows(const CasArgs &a, uint64_t *d_row, uint64_t *d_ksz, uint64_t *d_vsz,
+                     hipStream_t s)
+{
+    k_cas_rows<<<grid_for(a.E, BLOCK), BLOCK, 0, s>>>(a, d_row, d_ksz, d_vsz);
+}
+
+void launch_cas_emit(const CasArgs &a, const uint64_t *d_row, const uint64_t *d_orank,
+                     const uint64_t *d_kpos, const uint64_t *d_vpos, const uint64_t *d_arank,
+                     uint64_t seq_floor, uint64_t n_out, uint64_t kbytes, uint64_t vbytes,
+                     uint64_t *d_okoff, uint64_t *d_ovoff, uint64_t *d_osk, uint64_t *d_row_ksrc,
+                     uint64_t *d_row_vsrc, hipStream_t s)
+{
+    k_cas_emit<<<grid_for(a.E, BLOCK), BLOCK, 0, s>>>(a, d_row, d_orank, d_kpos, d_vpos, d_arank,
+                                                     seq_floor, n_out, kbytes, vbytes, d_okoff,
+                                                     d_ovoff, d_osk, d_row_ksrc, d_row_vsrc);
+}

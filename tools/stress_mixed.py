@@ -2,7 +2,9 @@
 """Mixed-operation GPU stress: randomized interleavings of every C-ABI
 entry point on one handle — writes, batched writes (rrdb_write_batch, which
 the oracle replays through put/remove), batched counter increments
-(rrdb_incr_batch, which the oracle replays through get/ttl/put), flushes, point/range/batched reads with
+(rrdb_incr_batch, which the oracle replays through get/ttl/put), batched
+check-and-mutate ops (rrdb_check_and_mutate_batch, which the oracle replays
+through get/ttl and the applied puts/removes), flushes, point/range/batched reads with
 the serving lanes forced on, pipelined count scans, paged scans, real
 compactions, checkpoints and restores — cross-checked against the CPU
 oracle driven with the same operation stream.  Complements tools/soak.py
@@ -76,6 +78,64 @@ def replay_incr(o, ops, now):
     return values, errors
 
 
+def validate_check(ct, operand, exist, value):
+    """the reference's validate_check: (passed, invalid_argument)"""
+    if ct <= 4:
+        return (True, not exist, not exist or not value, exist, exist and bool(value))[ct], False
+    if not exist:
+        return False, False
+    if ct <= 7:
+        if not operand:
+            return True, False
+        if len(value) < len(operand):
+            return False, False
+        return (operand in value, value.startswith(operand), value.endswith(operand))[ct - 5], False
+    a, b = value, operand
+    if ct >= 13:
+        a, b = buf2int64(value), buf2int64(operand)
+        if a is None or b is None:
+            return False, True
+    c = (a > b) - (a < b)
+    return (c < 0, c <= 0, c == 0, c >= 0, c > 0)[(ct - 8) % 5], False
+
+
+def replay_cas(o, ops, now):
+    """the batch on the oracle: every check key read before the first write
+    (an oracle read flushes), then the reference's check_and_mutate op by op
+    on a shadow of the touched keys, the applied puts and removes, one flush"""
+    assert o.flush() == OK
+    shadow = {}
+    for k in {op[0] for op in ops}:
+        e, val = o.get(k, now)
+        if e == OK:
+            _, ttl = o.ttl(k, now)
+            shadow[k] = (val, now + ttl if ttl > 0 else 0)
+    errors, exists, values = [], [], []
+    for ck, ct, operand, muts, ret in ops:
+        if not muts or not 0 <= ct <= 17:
+            errors.append(4)  # kInvalidArgument: a malformed op reads nothing
+            exists.append(False)
+            values.append(b"")
+            continue
+        old = shadow.get(ck)
+        exist = old is not None and not 0 < old[1] <= now
+        passed, invalid = validate_check(ct, operand, exist, old[0] if exist else b"")
+        exists.append(exist)
+        values.append(old[0] if exist and ret else b"")
+        errors.append(OK if passed else (4 if invalid else 13))  # 13 = kTryAgain
+        if passed:
+            for k, v, ets in muts:
+                hk, sk = D.restore_key(k)
+                if v is None:
+                    assert o.remove(hk, sk) == OK
+                    shadow[k] = None
+                else:
+                    assert o.put(hk, sk, v, ets, now) == OK
+                    shadow[k] = (v, ets)
+    assert o.flush() == OK
+    return errors, exists, values
+
+
 def main():
     steps = int(sys.argv[1]) if len(sys.argv) > 1 else 600
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 11
@@ -94,8 +154,27 @@ def main():
     tmp_o = tempfile.mkdtemp(prefix="stress_ckpt_o_")
     decree = 0
     for step in range(steps):
-        op = rnd.randrange(12)
-        if op == 11:  # batched increments: most stored values are no integers
+        op = rnd.randrange(13)
+        if op == 12:  # batched check-and-mutate: every check type, lists of up
+            # to three mutations on the check key's hashkey, now and then a
+            # malformed op (an empty list, a check type out of range)
+            ops = []
+            for _ in range(rnd.choice([1, 7, 300, 2049, 5000])):
+                hk = b"hk%03d" % rnd.randrange(70)
+                muts = [(D.generate_key(hk, b"s%02d" % rnd.randrange(7)),
+                         None if rnd.random() < 0.2 else rnd.choice([b"5", b"v7", b"0x10", b""]),
+                         rnd.choice([0, 0, 0, now + 50, now - 1]))
+                        for _ in range(rnd.choice([0, 1, 1, 1, 2, 3]))]
+                ops.append((D.generate_key(hk, b"s%02d" % rnd.randrange(7)),
+                            rnd.choice([-1, 18] + list(range(18)) * 3),
+                            rnd.choice([b"", b"v", b"5", b"7", b"16", b"v7", b"b1"]), muts,
+                            rnd.random() < 0.5))
+            err, errors, exists, values, st = g.check_and_mutate_batch(ops, now)
+            assert err == OK and st.input_ops == len(ops)
+            assert (errors, exists, values) == replay_cas(o, ops, now)
+            assert g.num_runs() == o.num_runs() and g.num_records() == o.num_records()
+            checks += 1
+        elif op == 11:  # batched increments: most stored values are no integers
             # (the op fails and writes nothing) until an incr has replaced them
             ops = [(D.generate_key(b"hk%03d" % rnd.randrange(70), b"s%02d" % rnd.randrange(7)),
                     rnd.choice([1, -1, 5, 2**62, -2**62]),
