@@ -226,6 +226,74 @@
  *     cas_lookup, cas_apply (walk and ranks), cas_emit (the run and the
  *     returned check values) and cas_total (device time).
  *
+ * Batched writes with timetags.  Duplication replays another cluster's put,
+ * remove, multi_put and multi_remove through pegasus_write_service::duplicate
+ * (pegasus_write_service.cpp:509-586) into rocksdb_wrapper::write_batch_put_ctx
+ * (rocksdb_wrapper.cpp:129-183): every write carries a timetag, and with
+ * verify_timetag set the stored record is read first and the write is dropped
+ * when that record is live and its timetag is not smaller.
+ * rrdb_write_batch_timetag takes n such ops unsorted, in commit order,
+ * duplicate keys allowed, and verifies and applies them on the device.  The
+ * call leaves behind exactly what this sequence leaves behind, ending in at
+ * most one new run: flush the memtable; for i = 0..n-1 apply op i as
+ * write_batch_put_ctx / write_batch_delete do, each with its own read;
+ * rrdb_flush.
+ *   - Keys, values, expire_ts and kinds are rrdb_write_batch's.  timetags[i]
+ *     is the finished 64-bit timetag, generate_timetag(timestamp, cluster_id,
+ *     deleted) = timestamp << 8 | cluster_id << 1 | deleted
+ *     (pegasus_value_schema.h:44-47).  The engine stores it and compares it as
+ *     an unsigned integer and never takes it apart.  A local write passes its
+ *     own timetag with verify[i] = 0; a duplicated write passes the remote
+ *     timetag and the request's verify_timetag.
+ *   - Per op, with `old` the newest version of the key at that moment,
+ *     earlier ops of this batch included:
+ *       DELETE: always applied (write_batch_delete makes no check, :221-239);
+ *         the record is a tombstone with an empty value and no timetag;
+ *       PUT with verify[i] != 0 on a handle whose pegasus.data_version >= 1:
+ *         ignored when `old` is live and timetag(old) >= timetags[i]; live
+ *         means a PUT whose stored expire is not (> 0 && <= epoch_now).
+ *         Nothing is stored for an ignored op and applied[i] = 0.  Otherwise
+ *         the op is applied;
+ *       any other PUT: applied.  Data version 0 has no timetag: verify is
+ *         without effect there and nothing is stored beyond the expire (the
+ *         reference's verify_timetag_compatible_with_version_0);
+ *       an applied PUT stores the header of the handle's data version with
+ *         the expire as rrdb_put computes it (expire_ts == 0 with a
+ *         default_ttl env becomes epoch_now + default_ttl), timetags[i]
+ *         big-endian in the 8 timetag bytes, then the user bytes;
+ *         applied[i] = 1.  A PUT that this batch stored with an expire already
+ *         past counts as not live for the ops after it, as rrdb_get would
+ *         report it.
+ *   - For a stale PUT the reference writes an empty key with an empty value
+ *     instead (:157-161), a record that lies before every key a read can
+ *     name.  The engine does not store it.
+ *   - Op i has seqno next_seq_floor + i and the floor advances by n_ops,
+ *     ignored and superseded ops included (the reference's empty record
+ *     consumes a sequence number too).  Per key only the last applied op is
+ *     stored.  If nothing is applied no run is added; the floor still
+ *     advances and the call returns kOk.
+ *   - With timetags == NULL and verify == NULL the call is rrdb_write_batch:
+ *     the run, the floor and the shared stat fields are the same.
+ *   - rrdb_put, rrdb_write_batch, rrdb_incr_batch and
+ *     rrdb_check_and_mutate_batch store timetag 0.  A verified PUT with a
+ *     timetag above 0 therefore beats their records, and a verified PUT with
+ *     timetag 0 loses against any live record.
+ *   - Pending memtable entries are older than the batch: they are flushed
+ *     first into a run of their own, and a failure of that flush is returned.
+ *   - Everything is validated before anything changes, as in
+ *     rrdb_write_batch and with the same list; timetags, verify and applied
+ *     are not validated (any value is meaningful).  n_ops == 0 is kOk and
+ *     does nothing.
+ *   - Every allocation proportional to the batch may fail cleanly: on a full
+ *     device the call returns kIOError, no run is added, the floor is
+ *     unchanged, applied is unspecified, and a memtable flush that already
+ *     happened stays.
+ *   - rrdb_phase_ms reports wbt_sort (sort and segments), wbt_lookup,
+ *     wbt_apply (the walk), wbt_emit and wbt_total (device time), and
+ *     wbt_stage and wbt_upload (host time of the staging and of the copies).
+ *     Env "engine.wbt_lane_max" (default 32) is the longest chain one lane
+ *     walks; a longer one is scanned by a whole wave.
+ *
  * Compaction route.  One compaction pass is a rank kernel followed by an emit
  * kernel, and which pair runs is decided per pass: from the envs
  * "engine.rank_mode" and "engine.emit_mode", the run count, the key shape of
@@ -389,6 +457,29 @@ int32_t rrdb_check_and_mutate_batch(
     const uint8_t *mut_kinds, const uint8_t *return_check_value, uint32_t epoch_now,
     int32_t *errors, uint8_t *check_exist, rrdb_result *check_values,
     rrdb_cas_batch_stats *stats);
+
+typedef struct {
+    uint64_t input_ops;       /* n_ops                                            */
+    uint64_t applied;         /* ops whose write took effect (applied[i] == 1)    */
+    uint64_t ignored;         /* verified PUTs dropped as stale (applied[i] == 0) */
+    uint64_t output_records;  /* records in the new run = keys with >= 1 applied op */
+    uint64_t superseded;      /* applied ops that are not their key's last applied op */
+    uint64_t puts, removes;   /* among the output records                         */
+    uint64_t key_bytes, value_bytes; /* of the new run (values encoded)           */
+} rrdb_timetag_batch_stats;   /* input_ops == ignored + superseded + output_records */
+
+/* Apply n_ops puts/removes that carry timetags, given unsorted in commit
+ * order with duplicate keys allowed, verified and applied on the device; see
+ * the header comment.  The first eight arguments are rrdb_write_batch's.
+ * timetags[n] may be null (all 0).  verify[n] may be null (none).
+ * applied[n]: caller-owned, may be null. */
+int32_t rrdb_write_batch_timetag(void *h, uint64_t n_ops,
+                                 const uint8_t *keys, const uint64_t *key_offs,
+                                 const uint8_t *values, const uint64_t *val_offs,
+                                 const uint32_t *expire_ts, const uint8_t *kinds,
+                                 const uint64_t *timetags, const uint8_t *verify,
+                                 uint32_t epoch_now, uint8_t *applied,
+                                 rrdb_timetag_batch_stats *stats);
 
 enum {
     RRDB_ROUTE_NONE = -1,

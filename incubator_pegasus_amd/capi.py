@@ -157,6 +157,20 @@ class _IncrBatchStats(C.Structure):
     ]
 
 
+class _TimetagBatchStats(C.Structure):
+    _fields_ = [
+        ("input_ops", C.c_uint64),
+        ("applied", C.c_uint64),
+        ("ignored", C.c_uint64),
+        ("output_records", C.c_uint64),
+        ("superseded", C.c_uint64),
+        ("puts", C.c_uint64),
+        ("removes", C.c_uint64),
+        ("key_bytes", C.c_uint64),
+        ("value_bytes", C.c_uint64),
+    ]
+
+
 class _CasBatchStats(C.Structure):
     _fields_ = [
         ("input_ops", C.c_uint64),
@@ -190,6 +204,19 @@ class IncrBatchStats:
     failed_parse: int = 0
     failed_range: int = 0
     output_records: int = 0
+    key_bytes: int = 0
+    value_bytes: int = 0
+
+
+@dataclass
+class TimetagBatchStats:
+    input_ops: int = 0
+    applied: int = 0
+    ignored: int = 0
+    output_records: int = 0
+    superseded: int = 0
+    puts: int = 0
+    removes: int = 0
     key_bytes: int = 0
     value_bytes: int = 0
 
@@ -382,6 +409,12 @@ class RrdbLib:
             L.rrdb_incr_batch.argtypes = [
                 C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                 C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(_IncrBatchStats)]
+        self.has_write_batch_timetag = hasattr(L, "rrdb_write_batch_timetag")
+        if self.has_write_batch_timetag:
+            L.rrdb_write_batch_timetag.restype = C.c_int32
+            L.rrdb_write_batch_timetag.argtypes = (
+                [C.c_void_p, C.c_uint64] + [C.c_void_p] * 8 +
+                [C.c_uint32, C.c_void_p, C.POINTER(_TimetagBatchStats)])
         self.has_check_and_mutate_batch = hasattr(L, "rrdb_check_and_mutate_batch")
         if self.has_check_and_mutate_batch:
             L.rrdb_check_and_mutate_batch.restype = C.c_int32
@@ -897,6 +930,62 @@ class RrdbPartition:
         expire = np.array([o[2] for o in ops], dtype=np.int32)
         err, nv, er, stats = self.incr_batch_arrays(keys, koffs, inc, expire, epoch_now)
         return err, [int(x) for x in nv], [int(x) for x in er], stats
+
+    # ---- batched writes with timetags: engine-only (include/rrdb_engine_ext.h) ----
+    def _need_write_batch_timetag(self):
+        if not self.lib.has_write_batch_timetag:
+            raise RuntimeError(
+                f"write_batch_timetag: backend {self.lib.backend!r} ({self.lib.path}) does not "
+                "export rrdb_write_batch_timetag (engine-only extension)")
+
+    def write_batch_timetag_arrays(self, keys_u8, key_offs_u64, vals_u8, val_offs_u64,
+                                   expire_u32, kinds_u8, timetags_u64, verify_u8,
+                                   epoch_now: int = 0):
+        """write_batch_timetag from packed numpy arrays (no python loop; the
+        bench and the rejection tests, which hand in malformed arrays, use it).
+        timetags_u64 and verify_u8 may be None (all zero).  Returns
+        (err, applied uint8 array, TimetagBatchStats)."""
+        import numpy as np
+
+        self._need_write_batch_timetag()
+        for a, dt in ((keys_u8, np.uint8), (key_offs_u64, np.uint64), (vals_u8, np.uint8),
+                      (val_offs_u64, np.uint64), (expire_u32, np.uint32), (kinds_u8, np.uint8),
+                      (timetags_u64, np.uint64), (verify_u8, np.uint8)):
+            assert a is None or (a.dtype == dt and a.flags["C_CONTIGUOUS"]), (a.dtype, dt)
+        n = len(kinds_u8)
+        applied = np.zeros(n, dtype=np.uint8)
+        st = _TimetagBatchStats()
+        err = self._L.rrdb_write_batch_timetag(
+            self._h, n,
+            keys_u8.ctypes.data_as(C.c_void_p), key_offs_u64.ctypes.data_as(C.c_void_p),
+            vals_u8.ctypes.data_as(C.c_void_p), val_offs_u64.ctypes.data_as(C.c_void_p),
+            expire_u32.ctypes.data_as(C.c_void_p), kinds_u8.ctypes.data_as(C.c_void_p),
+            None if timetags_u64 is None else timetags_u64.ctypes.data_as(C.c_void_p),
+            None if verify_u8 is None else verify_u8.ctypes.data_as(C.c_void_p),
+            epoch_now, applied.ctypes.data_as(C.c_void_p), C.byref(st))
+        stats = TimetagBatchStats(**{f[0]: getattr(st, f[0])
+                                     for f in _TimetagBatchStats._fields_})
+        return err, applied, stats
+
+    def write_batch_timetag(self, ops, epoch_now: int = 0):
+        """Apply `ops`, a list of (full_key, value_or_None, expire_ts, timetag,
+        verify) in commit order (None = remove; duplicate keys allowed: each
+        op sees the ones before it), as the reference's duplicate handler
+        would, one after the other, on the device.  A verified PUT is dropped
+        when the stored record is live and its timetag is not smaller.
+        Returns (err, applied_list, TimetagBatchStats)."""
+        import numpy as np
+
+        self._need_write_batch_timetag()
+        keys, koffs = _pack([o[0] for o in ops])
+        vals, voffs = _pack([o[1] if o[1] is not None else b"" for o in ops])
+        expire = np.array([o[2] if o[1] is not None else 0 for o in ops], dtype=np.uint32)
+        kinds = np.array([0 if o[1] is not None else 1 for o in ops], dtype=np.uint8)
+        timetags = np.array([o[3] for o in ops], dtype=np.uint64)
+        verify = np.array([1 if o[4] else 0 for o in ops], dtype=np.uint8)
+        err, ap, stats = self.write_batch_timetag_arrays(keys, koffs, vals, voffs, expire, kinds,
+                                                         timetags, verify, epoch_now)
+        return err, [int(x) for x in ap], stats
 
     # ---- batched check-and-mutate: engine-only (include/rrdb_engine_ext.h) ----
     def _need_check_and_mutate_batch(self):

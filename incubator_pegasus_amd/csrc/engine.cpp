@@ -163,8 +163,15 @@ void launch_cas_rows(const CasArgs &, uint64_t *, uint64_t *, uint64_t *, hipStr
 void launch_cas_emit(const CasArgs &, const uint64_t *, const uint64_t *, const uint64_t *,
                      const uint64_t *, const uint64_t *, uint64_t, uint64_t, uint64_t, uint64_t,
                      uint64_t *, uint64_t *, uint64_t *, uint64_t *, uint64_t *, hipStream_t);
+void launch_wbt_heads(const WbKeys &, uint64_t, const uint64_t *, const uint32_t *, uint64_t *,
+                      uint64_t *, hipStream_t);
+void launch_wbt_walk(const TtArgs &, hipStream_t);
+void launch_wbt_scatter(const TtArgs &, uint64_t, const uint64_t *, const uint64_t *,
+                        const uint64_t *, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t,
+                        uint64_t, uint64_t *, uint64_t *, uint64_t *, uint64_t *, uint64_t *,
+                        hipStream_t);
 
-#define HIP_OK(x)                                                                                 \
+#define HIP_OK(x)                                                                                \
     do {                                                                                           \
         hipError_t e_ = (x);                                                                       \
         if (e_ != hipSuccess) {                                                                    \
@@ -697,6 +704,9 @@ struct HipEngine {
     /* rrdb_incr_batch: longest segment one lane walks (env
      * "engine.incr_lane_max"); longer ones get a wave */
     uint32_t incr_lane_max = INCR_LANE_MAX;
+    /* rrdb_write_batch_timetag: the same threshold for its walk (env
+     * "engine.wbt_lane_max") */
+    uint32_t wbt_lane_max = WBT_LANE_MAX;
     bool bloom_enabled = true; /* env "rocksdb.filter_type": common(default)|none */
     uint32_t max_iter_count = 1000, mg_max_iter_count = 3000;
     uint64_t mg_max_iter_size = 30ull << 20, iter_time_ms = 30000;
@@ -1800,6 +1810,9 @@ int32_t rrdb_set_envs(void *h, const char *const *keys, const char *const *value
         } else if (k == "engine.incr_lane_max") {
             long long t = atoll(v.c_str());
             e->incr_lane_max = t < 1 ? 1u : (uint32_t)std::min<long long>(t, 1 << 20);
+        } else if (k == "engine.wbt_lane_max") {
+            long long t = atoll(v.c_str());
+            e->wbt_lane_max = t < 1 ? 1u : (uint32_t)std::min<long long>(t, 1 << 20);
         } else if (k == "rocksdb.usage_scenario") {
             /* bulk_load sets level0_file_num_compaction_trigger to -1, i.e.
              * no automatic compaction (set_usage_scenario); normal and
@@ -4412,6 +4425,275 @@ int32_t rrdb_incr_batch(void *h, uint64_t n_ops, const uint8_t *keys, const uint
     e->runs.push_back(r);
     e->runs_changed();
     e->next_seq_floor += red[IR_APPLIED];
+    results_out();
+    return RRDB_OK;
+}
+
+/* ---- batched writes with timetags (rrdb_write_batch_timetag,
+ * rrdb_engine_ext.h) ----
+ * The host validates (wb_validate), stages the values with the timetag in
+ * the header and folds every op to its TT_OP_* bits (wb_stage_values_tt) and
+ * uploads once; the device sorts, looks the bases up, walks every key's chain
+ * with the rule of tt_verify.h and emits the run (kernels.hip, "timetag
+ * batch").  Two read-backs: the totals before the run is allocated, and
+ * `applied` at the end when the caller asked for it. */
+int32_t rrdb_write_batch_timetag(void *h, uint64_t n_ops, const uint8_t *keys,
+                                 const uint64_t *key_offs, const uint8_t *values,
+                                 const uint64_t *val_offs, const uint32_t *expire_ts,
+                                 const uint8_t *kinds, const uint64_t *timetags,
+                                 const uint8_t *verify, uint32_t epoch_now, uint8_t *applied,
+                                 rrdb_timetag_batch_stats *stats)
+{
+    if (stats)
+        *stats = rrdb_timetag_batch_stats{};
+    if (!h)
+        return RRDB_INVALID_ARGUMENT;
+    auto *e = (HipEngine *)h;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (n_ops == 0)
+        return RRDB_OK;
+    using clk = std::chrono::steady_clock;
+    auto ms_since = [](clk::time_point t0) {
+        return std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+    };
+    const auto t_host = clk::now();
+    if (e->pend.active || e->pend_scan.active)
+        return RRDB_INVALID_ARGUMENT;
+    if (!wb_validate(n_ops, keys, key_offs, values, val_offs, kinds))
+        return RRDB_INVALID_ARGUMENT;
+    const uint64_t n = n_ops;
+    uint64_t sv_bytes = 0;
+    if (!wb_staged_bytes(n, val_offs, kinds, e->data_version, &sv_bytes))
+        return RRDB_INVALID_ARGUMENT;
+
+    /* pending memtable entries are older than the batch: their own run first */
+    e->activate();
+    int32_t rc = engine_flush(e);
+    if (rc != RRDB_OK)
+        return rc;
+
+    /* staging: keys verbatim, values with header and timetag in front of
+     * every PUT, and the op flags the walk reads */
+    WbBufs hb;
+    uint8_t *h_svals = hb.get_host<uint8_t>(sv_bytes);
+    uint64_t *h_svoff = hb.get_host<uint64_t>((n + 1) * 8);
+    uint8_t *h_flags = hb.get_host<uint8_t>(n);
+    if (!hb.ok)
+        return RRDB_IO_ERROR;
+    wb_stage_values_tt(n, values, val_offs, expire_ts, kinds, timetags, verify, e->data_version,
+                       e->default_ttl, epoch_now, h_svals, h_svoff, h_flags);
+    const uint64_t in_fk = wb_fixed_stride(key_offs, n), in_kbytes = key_offs[n];
+    e->phase_ms["wbt_stage"] = ms_since(t_host);
+
+    /* every device buffer proportional to the batch is carved from one try
+     * allocation: the later ones (per segment, per output row) by their upper
+     * bound n.  Without a verified op no base can matter: no lookup. */
+    const auto t_up = clk::now();
+    const int R = (int)e->runs.size();
+    const bool lookup = R > 0 && verify != nullptr && e->data_version >= 1;
+    IncrSlab b;
+    uint8_t *d_keys = nullptr, *d_svals = nullptr, *d_flags = nullptr, *d_applied = nullptr;
+    uint64_t *d_koff = nullptr, *d_svoff = nullptr, *d_tt = nullptr, *d_w0 = nullptr,
+             *d_w1 = nullptr, *d_head = nullptr, *d_hrank = nullptr, *d_seg_start = nullptr,
+             *d_psc = nullptr, *d_hit = nullptr, *d_ulen = nullptr, *d_seg_has = nullptr,
+             *d_orank = nullptr, *d_seg_ksz = nullptr, *d_seg_vsz = nullptr, *d_red = nullptr,
+             *d_kpos = nullptr, *d_vpos = nullptr, *d_row_ksrc = nullptr, *d_row_vsrc = nullptr,
+             *d_kanch = nullptr, *d_vanch = nullptr;
+    int32_t *d_status = nullptr;
+    uint32_t *d_lcp = nullptr, *d_i0 = nullptr, *d_i1 = nullptr, *d_expire = nullptr,
+             *d_seg_last = nullptr;
+    for (int pass = 0; pass < 2; pass++) { /* 0 sizes the slab, 1 hands the pieces out */
+        b.take(&d_keys, in_kbytes);
+        b.take(&d_koff, (n + 1) * 8); /* the lookup takes offsets */
+        b.take(&d_svals, sv_bytes);
+        b.take(&d_svoff, (n + 1) * 8);
+        b.take(&d_flags, n);
+        b.take(&d_tt, n * 8);
+        b.take(&d_lcp, 256);
+        b.take(&d_w0, n * 8);
+        b.take(&d_w1, n * 8);
+        b.take(&d_i0, n * 4);
+        b.take(&d_i1, n * 4);
+        b.take(&d_head, n * 8);
+        b.take(&d_hrank, n * 8);
+        b.take(&d_seg_start, (n + 1) * 8);
+        b.take(&d_psc, psum_scratch_elems(n) * 8);
+        if (lookup) {
+            b.take(&d_status, n * 4);
+            b.take(&d_hit, n * 8);
+            b.take(&d_ulen, n * 8);
+            b.take(&d_expire, n * 4);
+        }
+        b.take(&d_applied, n);
+        b.take(&d_seg_last, n * 4);
+        b.take(&d_seg_has, n * 8);
+        b.take(&d_orank, n * 8);
+        b.take(&d_seg_ksz, n * 8);
+        b.take(&d_seg_vsz, n * 8);
+        b.take(&d_red, TR_WORDS * 8);
+        b.take(&d_kpos, n * 8);
+        b.take(&d_vpos, n * 8);
+        b.take(&d_row_ksrc, n * 8);
+        b.take(&d_row_vsrc, n * 8);
+        b.take(&d_kanch, (((in_kbytes + 15) >> 10) + 2) * 8);
+        b.take(&d_vanch, (((sv_bytes + 15) >> 10) + 2) * 8);
+        if (pass == 0 && !b.commit())
+            return RRDB_IO_ERROR;
+    }
+    b.upload(d_keys, keys, in_kbytes);
+    b.upload(d_koff, key_offs, (n + 1) * 8);
+    b.upload(d_svals, h_svals, sv_bytes);
+    b.upload(d_svoff, h_svoff, (n + 1) * 8);
+    b.upload(d_flags, h_flags, n);
+    if (timetags) {
+        b.upload(d_tt, timetags, n * 8);
+    } else if (b.ok && hipMemset(d_tt, 0, n * 8) != hipSuccess) {
+        (void)hipGetLastError();
+        b.ok = false;
+    }
+    if (!b.ok)
+        return RRDB_IO_ERROR;
+    e->phase_ms["wbt_upload"] = ms_since(t_up);
+
+    hipEvent_t ev[6];
+    for (auto &x : ev)
+        HIP_OK(hipEventCreate(&x));
+    auto drop_events = [&] {
+        for (auto &x : ev)
+            (void)hipEventDestroy(x);
+    };
+    /* sort, then the segments: one per distinct key */
+    const WbKeys wk{d_keys, in_fk ? nullptr : d_koff, in_fk, d_lcp};
+    HIP_OK(hipEventRecord(ev[0], e->stream));
+    const int cur = launch_wb_sort(wk, n, d_lcp, d_w0, d_i0, d_w1, d_i1, e->stream);
+    const uint64_t *d_w = cur ? d_w1 : d_w0;
+    const uint32_t *d_ix = cur ? d_i1 : d_i0;
+    launch_wbt_heads(wk, n, d_w, d_ix, d_head, d_red, e->stream);
+    launch_psum(d_head, d_hrank, n, d_psc, e->stream);
+    launch_incr_segs(n, d_head, d_hrank, d_seg_start, d_red, e->stream);
+    HIP_OK(hipEventRecord(ev[1], e->stream));
+
+    /* the bases: every op's key against the runs as they are now */
+    DevRun *dr = lookup ? e->dev_runs() : nullptr;
+    if (lookup)
+        launch_get(dr, R, d_keys, d_koff, n, epoch_now, e->data_version, d_status, d_hit, d_ulen,
+                   d_expire, e->stream);
+    HIP_OK(hipEventRecord(ev[2], e->stream));
+
+    TtArgs a{};
+    a.k = wk;
+    a.n = n;
+    a.ix = d_ix;
+    a.seg_start = d_seg_start;
+    a.flags = d_flags;
+    a.tt = d_tt;
+    a.svals = d_svals;
+    a.svoff = d_svoff;
+    a.status = d_status;
+    a.hit = d_hit;
+    a.runs = dr;
+    a.data_version = e->data_version;
+    a.lane_max = e->wbt_lane_max;
+    a.applied = d_applied;
+    a.seg_last = d_seg_last;
+    a.seg_has = d_seg_has;
+    a.seg_ksz = d_seg_ksz;
+    a.seg_vsz = d_seg_vsz;
+    a.red = (unsigned long long *)d_red;
+    launch_wbt_walk(a, e->stream);
+    HIP_OK(hipEventRecord(ev[3], e->stream));
+
+    /* the totals: one read */
+    uint64_t red[TR_WORDS];
+    HIP_OK(hipMemcpyAsync(red, d_red, sizeof(red), hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipStreamSynchronize(e->stream));
+    const uint64_t n_seg = red[TR_NSEG], n_out = red[TR_NOUT];
+    const uint64_t kbytes = red[TR_KBYTES], vbytes = red[TR_VBYTES];
+    auto u32_or_0 = [](uint64_t v) { return v > UINT32_MAX ? 0u : (uint32_t)v; };
+    const uint32_t out_fk = n_out && red[TR_KMIN] == red[TR_KMAX] ? u32_or_0(red[TR_KMIN]) : 0;
+    const uint32_t out_fv = n_out && red[TR_VMIN] == red[TR_VMAX] ? u32_or_0(red[TR_VMIN]) : 0;
+
+    auto results_out = [&]() {
+        if (applied)
+            HIP_OK(hipMemcpy(applied, d_applied, n, hipMemcpyDeviceToHost));
+        if (stats) {
+            stats->input_ops = n;
+            stats->applied = red[TR_APPLIED];
+            stats->ignored = red[TR_IGNORED];
+            stats->output_records = n_out;
+            stats->superseded = red[TR_APPLIED] - n_out;
+            stats->puts = red[TR_PUTS];
+            stats->removes = n_out - red[TR_PUTS];
+            stats->key_bytes = kbytes;
+            stats->value_bytes = vbytes;
+        }
+    };
+    auto timers = [&](bool emitted) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
+            e->phase_ms["wbt_sort"] = ms;
+        if (hipEventElapsedTime(&ms, ev[1], ev[2]) == hipSuccess)
+            e->phase_ms["wbt_lookup"] = ms;
+        if (hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess)
+            e->phase_ms["wbt_apply"] = ms;
+        e->phase_ms["wbt_emit"] = 0.0;
+        if (emitted && hipEventElapsedTime(&ms, ev[4], ev[5]) == hipSuccess)
+            e->phase_ms["wbt_emit"] = ms;
+        float tot = 0;
+        if (hipEventElapsedTime(&tot, ev[0], ev[3]) == hipSuccess)
+            e->phase_ms["wbt_total"] = tot + e->phase_ms["wbt_emit"];
+    };
+    if (n_seg > n || n_out > n_seg || red[TR_APPLIED] + red[TR_IGNORED] != n ||
+        red[TR_APPLIED] < n_out || kbytes > in_kbytes || vbytes > sv_bytes) {
+        drop_events(); /* cannot happen: the walk's totals contradict the batch */
+        return RRDB_IO_ERROR;
+    }
+    if (n_out == 0) { /* every op was ignored: no run; the seqnos are spent all the same */
+        timers(false);
+        drop_events();
+        e->next_seq_floor += n;
+        results_out();
+        return RRDB_OK;
+    }
+
+    RunBuf r;
+    if (out_fk)
+        d_kpos = nullptr;
+    if (out_fv)
+        d_vpos = nullptr;
+    if (!e->alloc_base(r, n_out, kbytes, vbytes, RunAlloc::Try)) {
+        drop_events();
+        return RRDB_IO_ERROR;
+    }
+    /* the strides detect_fixed_* would report for the emitted run */
+    r.fixed_klen = out_fk;
+    r.fixed_vlen = out_fv;
+    r.fixed_vlen_put =
+        red[TR_PUTS] && red[TR_PVMIN] == red[TR_PVMAX] ? u32_or_0(red[TR_PVMIN]) : 0;
+    HIP_OK(hipEventRecord(ev[4], e->stream));
+    launch_psum(d_seg_has, d_orank, n_seg, d_psc, e->stream);
+    if (d_kpos)
+        launch_psum(d_seg_ksz, d_kpos, n_seg, d_psc, e->stream);
+    if (d_vpos)
+        launch_psum(d_seg_vsz, d_vpos, n_seg, d_psc, e->stream);
+    launch_wbt_scatter(a, n_seg, d_orank, d_kpos, d_vpos, e->next_seq_floor, n_out, kbytes, vbytes,
+                       out_fk, out_fv, r.koff, r.voff, r.sk, d_row_ksrc, d_row_vsrc, e->stream);
+    launch_split_copy(d_row_ksrc, r.koff, n_out, r.fixed_klen, kbytes, d_kanch, r.keys,
+                      e->stream);
+    launch_split_copy(d_row_vsrc, r.voff, n_out, r.fixed_vlen, vbytes, d_vanch, r.vals,
+                      e->stream);
+    HIP_OK(hipEventRecord(ev[5], e->stream));
+    if (!e->finish_run(r, nullptr, RunAlloc::Try, e->bloom_enabled)) {
+        e->free_run(r);
+        drop_events();
+        return RRDB_IO_ERROR;
+    }
+    timers(true);
+    drop_events();
+
+    e->runs.push_back(r);
+    e->runs_changed();
+    e->next_seq_floor += n;
     results_out();
     return RRDB_OK;
 }

@@ -94,6 +94,45 @@ struct IncrArgs {
     unsigned long long *red; /* IR_* */
 };
 
+/* timetag batch (rrdb_write_batch_timetag).  Segments as in the incr batch; a
+ * segment of up to WBT_LANE_MAX ops is walked by one lane, a longer one gets a
+ * wave.  Env "engine.wbt_lane_max" overrides it per handle
+ * (tools/bench_timetag_batch.py sweeps it). */
+#define WBT_LANE_MAX 32
+
+/* timetag-batch reduction (one block of u64 words, vector atomics).  TR_NSEG
+ * is IR_NSEG: the segment kernel is the incr batch's. */
+enum {
+    TR_NSEG = 0, TR_APPLIED, TR_IGNORED, TR_NOUT, TR_PUTS, TR_KBYTES, TR_VBYTES,
+    TR_KMIN, TR_KMAX, TR_VMIN, TR_VMAX, TR_PVMIN, TR_PVMAX, TR_WORDS
+};
+
+#define WBT_NO_OP 0xFFFFFFFFu
+
+/* everything the walk and scatter kernels of rrdb_write_batch_timetag share,
+ * by value */
+struct TtArgs {
+    WbKeys k;              /* the uploaded keys, op order                       */
+    uint64_t n;            /* ops                                               */
+    const uint32_t *ix;    /* [n] sorted position -> op (key asc, op desc)      */
+    const uint64_t *seg_start; /* [n_seg + 1] sorted position of each segment  */
+    const uint8_t *flags;  /* [n] TT_OP_* (tt_verify.h), op order               */
+    const uint64_t *tt;    /* [n] timetags, op order                            */
+    const uint8_t *svals;  /* staged values (wb_stage.h), op order              */
+    const uint64_t *svoff; /* [n+1]                                             */
+    /* the lookup of every op's key against the runs (launch_get), op order;
+     * status null = no lookup was made, every base is dead */
+    const int32_t *status;
+    const uint64_t *hit;
+    const DevRun *runs;
+    uint32_t data_version, lane_max;
+    uint8_t *applied;      /* [n] op order, 1 = the op's write took effect      */
+    /* per segment */
+    uint32_t *seg_last;    /* the newest applied op, WBT_NO_OP when none        */
+    uint64_t *seg_has, *seg_ksz, *seg_vsz;
+    unsigned long long *red; /* TR_* */
+};
+
 /* cas batch (rrdb_check_and_mutate_batch) reduction (one block of u64 words,
  * vector atomics).  CR_NGRP is the number of hashkey groups; CR_PASSED ..
  * CR_RETBYTES come from the walk, the rest from the output rows. */

@@ -4817,3 +4817,330 @@ void launch_cas_emit(const CasArgs &a, const uint64_t *d_row, const uint64_t *d_
                                                      seq_floor, n_out, kbytes, vbytes, d_okoff,
                                                      d_ovoff, d_osk, d_row_ksrc, d_row_vsrc);
 }
+
+/* ================= timetag batch (rrdb_write_batch_timetag) =================
+ * n puts / removes that carry a timetag, unsorted, duplicate keys allowed,
+ * applied as the sequence write_batch_put_ctx / write_batch_delete per op
+ * would apply them (a verified PUT reads the stored timetag first and is
+ * dropped when that one is not smaller), ending in one run:
+ *   sort:     launch_wb_sort, unchanged.  Within a key the ops stand newest
+ *             first, so a chain is walked from the segment's end to its start.
+ *   segments: the incr batch's head and segment kernels.
+ *   lookup:   launch_get on the uploaded op arrays; the base state of a
+ *             segment is live with the timetag of the hit's value header, or
+ *             dead.  Skipped on data version 0 and when no op is verified.
+ *   walk:     tt_verify.h.  A segment of up to lane_max ops is walked by one
+ *             lane with tt_step.  A longer one gets a wave: if no PUT of it
+ *             stores an expire already past, the state in front of op j is a
+ *             segmented exclusive max-scan over (reset, present, timetag),
+ *             64 ops at a time with a carried element; else lane 0 walks it.
+ *   rank:     launch_psum of "segment has an applied op" gives the output row.
+ *   emit:     sk = (floor + op) << 1 | kind of the newest applied op, offsets
+ *             and row sources by row; launch_split_copy moves keys and staged
+ *             values.
+ * Every result is a function of the sorted order alone, so it does not depend
+ * on the grid or on scheduling. */
+#include "tt_verify.h"
+
+static_assert(TR_NSEG == IR_NSEG, "k_incr_segs writes the segment count");
+
+struct TtTally {
+    unsigned long long applied = 0, ignored = 0, nout = 0, puts = 0, kbytes = 0, vbytes = 0;
+    unsigned long long kmin = ~0ull, kmax = 0, vmin = ~0ull, vmax = 0, pvmin = ~0ull, pvmax = 0;
+};
+
+/* the newest stored version of op i's key, as the lookup found it */
+__device__ static inline TtState wbt_base(const TtArgs &a, uint32_t i)
+{
+    TtState b{0, 0};
+    if (!a.status || a.status[i] != 0)
+        return b; /* absent, tombstone or expired */
+    const uint64_t id = a.hit[i];
+    uint64_t vl;
+    const uint8_t *v = run_val(a.runs[id >> 40], id & 0xFFFFFFFFFFull, &vl);
+    const uint32_t off = a.data_version == 2 ? 5u : 4u;
+    b.live = 1;
+    if (a.data_version >= 1 && vl >= off + 8) {
+        uint64_t t;
+        __builtin_memcpy(&t, v + off, 8);
+        b.timetag = __builtin_bswap64(t);
+    }
+    return b;
+}
+
+/* what segment s leaves behind: its newest applied op */
+__device__ static inline void wbt_seg_out(const TtArgs &a, uint64_t s, uint32_t last, TtTally &t)
+{
+    uint64_t kl = 0, vl = 0;
+    if (last != WBT_NO_OP) {
+        (void)wb_key(a.k, last, &kl);
+        vl = a.svoff[last + 1] - a.svoff[last];
+        t.nout++;
+        t.kbytes += kl;
+        t.vbytes += vl;
+        t.kmin = kl < t.kmin ? kl : t.kmin;
+        t.kmax = kl > t.kmax ? kl : t.kmax;
+        t.vmin = vl < t.vmin ? vl : t.vmin;
+        t.vmax = vl > t.vmax ? vl : t.vmax;
+        if (!(a.flags[last] & TT_OP_DELETE)) {
+            t.puts++;
+            t.pvmin = vl < t.pvmin ? vl : t.pvmin;
+            t.pvmax = vl > t.pvmax ? vl : t.pvmax;
+        }
+    }
+    a.seg_last[s] = last;
+    a.seg_has[s] = last != WBT_NO_OP ? 1 : 0;
+    a.seg_ksz[s] = kl;
+    a.seg_vsz[s] = vl;
+}
+
+/* segment s = sorted positions [beg, end), walked oldest op first by one
+ * lane: the reference's sequence, op by op */
+__device__ static void wbt_walk(const TtArgs &a, uint64_t s, uint64_t beg, uint64_t end,
+                                TtState st, TtTally &t)
+{
+    uint32_t last = WBT_NO_OP;
+    for (uint64_t q = end; q-- > beg;) {
+        const uint32_t i = a.ix[q];
+        const bool ap = tt_step(&st, a.flags[i], a.tt[i]);
+        a.applied[i] = ap ? 1 : 0;
+        if (ap) {
+            last = i;
+            t.applied++;
+        } else {
+            t.ignored++;
+        }
+    }
+    wbt_seg_out(a, s, last, t);
+}
+
+__device__ static inline bool wbt_is_min(int w)
+{
+    return w == TR_KMIN || w == TR_VMIN || w == TR_PVMIN;
+}
+__device__ static inline bool wbt_is_max(int w)
+{
+    return w == TR_KMAX || w == TR_VMAX || w == TR_PVMAX;
+}
+
+/* block-level then device-level fold of the per-thread tallies */
+__device__ static inline void wbt_tally_flush(const TtTally &t, unsigned long long *s_red,
+                                              unsigned long long *red)
+{
+    if (threadIdx.x < TR_WORDS)
+        s_red[threadIdx.x] = wbt_is_min(threadIdx.x) ? ~0ull : 0ull;
+    __syncthreads();
+    if (t.applied)
+        atomicAdd(&s_red[TR_APPLIED], t.applied);
+    if (t.ignored)
+        atomicAdd(&s_red[TR_IGNORED], t.ignored);
+    if (t.nout) {
+        atomicAdd(&s_red[TR_NOUT], t.nout);
+        atomicAdd(&s_red[TR_KBYTES], t.kbytes);
+        atomicAdd(&s_red[TR_VBYTES], t.vbytes);
+        atomicMin(&s_red[TR_KMIN], t.kmin);
+        atomicMax(&s_red[TR_KMAX], t.kmax);
+        atomicMin(&s_red[TR_VMIN], t.vmin);
+        atomicMax(&s_red[TR_VMAX], t.vmax);
+        if (t.puts) {
+            atomicAdd(&s_red[TR_PUTS], t.puts);
+            atomicMin(&s_red[TR_PVMIN], t.pvmin);
+            atomicMax(&s_red[TR_PVMAX], t.pvmax);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x > TR_NSEG && threadIdx.x < TR_WORDS) {
+        const unsigned long long v = s_red[threadIdx.x];
+        if (wbt_is_min(threadIdx.x))
+            atomicMin(&red[threadIdx.x], v);
+        else if (wbt_is_max(threadIdx.x))
+            atomicMax(&red[threadIdx.x], v);
+        else if (v)
+            atomicAdd(&red[threadIdx.x], v);
+    }
+}
+
+/* segments of up to lane_max ops: one lane each */
+__global__ void __launch_bounds__(BLOCK) k_wbt_walk_lane(TtArgs a)
+{
+    __shared__ unsigned long long s_red[TR_WORDS];
+    TtTally t;
+    const uint64_t ns = a.red[TR_NSEG];
+    for (uint64_t s = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; s < ns;
+         s += gridDim.x * (uint64_t)blockDim.x) {
+        const uint64_t beg = a.seg_start[s], end = a.seg_start[s + 1];
+        if (end <= beg || end > a.n || end - beg > a.lane_max)
+            continue;
+        wbt_walk(a, s, beg, end, wbt_base(a, a.ix[beg]), t);
+    }
+    wbt_tally_flush(t, s_red, a.red);
+}
+
+__device__ static inline TtScan wbt_shfl_up(TtScan v, int off)
+{
+    TtScan r;
+    r.rp = __shfl_up(v.rp, off, WAVE);
+    r.max = __shfl_up((unsigned long long)v.max, off, WAVE);
+    return r;
+}
+
+/* a long segment on a whole wave; every lane enters with the same s.  The
+ * op indices of WBT_WAVE_UNROLL strides of 64 are loaded first, then their
+ * flags and timetags, then the scans run, so that the dependent loads of a
+ * stride overlap with its neighbours' (k_incr_chain_wave's staging). */
+#define WBT_WAVE_UNROLL 4
+__device__ static void wbt_seg_wave(const TtArgs &a, uint64_t s, int lane, TtTally &t)
+{
+    const uint64_t beg = a.seg_start[s], end = a.seg_start[s + 1];
+    if (end <= beg || end > a.n)
+        return;
+    const TtState b = wbt_base(a, a.ix[beg]); /* same address in every lane */
+    /* first pass: the scan holds only while every applied PUT is live */
+    bool past = false;
+    for (uint64_t q = beg + lane; q < end; q += WAVE)
+        past |= (a.flags[a.ix[q]] & TT_OP_PAST) != 0;
+    if (__any(past)) {
+        if (lane == 0)
+            wbt_walk(a, s, beg, end, b, t);
+        return;
+    }
+    const uint64_t len = end - beg;
+    TtScan carry{b.live ? 1u : 0u, b.live ? b.timetag : 0};
+    uint32_t last = WBT_NO_OP;
+    unsigned long long n_applied = 0;
+    for (uint64_t c = 0; c < len; c += WAVE * WBT_WAVE_UNROLL) {
+        uint32_t iu[WBT_WAVE_UNROLL];
+        uint32_t fu[WBT_WAVE_UNROLL];
+        uint64_t tu[WBT_WAVE_UNROLL];
+#pragma unroll
+        for (int u = 0; u < WBT_WAVE_UNROLL; u++) {
+            const uint64_t q = c + (uint64_t)u * WAVE + lane; /* chain position */
+            iu[u] = q < len ? a.ix[end - 1 - q] : WBT_NO_OP;
+        }
+#pragma unroll
+        for (int u = 0; u < WBT_WAVE_UNROLL; u++) {
+            const bool in = iu[u] != WBT_NO_OP;
+            fu[u] = in ? a.flags[iu[u]] : 0;
+            tu[u] = in ? a.tt[iu[u]] : 0;
+        }
+#pragma unroll
+        for (int u = 0; u < WBT_WAVE_UNROLL; u++) {
+            if (c + (uint64_t)u * WAVE >= len)
+                break; /* the same in every lane */
+            const bool in = iu[u] != WBT_NO_OP;
+            TtScan v = in ? tt_scan_elem((uint8_t)fu[u], tu[u]) : TtScan{0u, 0};
+            for (int off = 1; off < WAVE; off <<= 1) {
+                const TtScan up = wbt_shfl_up(v, off);
+                if (lane >= off)
+                    v = tt_scan_combine(up, v);
+            }
+            TtScan ex = wbt_shfl_up(v, 1);
+            if (lane == 0)
+                ex = TtScan{0u, 0};
+            const TtScan before = tt_scan_combine(carry, ex);
+            const TtScan tot = tt_scan_combine(carry, v);
+            carry.rp = __shfl(tot.rp, WAVE - 1, WAVE);
+            carry.max = __shfl((unsigned long long)tot.max, WAVE - 1, WAVE);
+            const bool ap = in && tt_scan_applied(before, (uint8_t)fu[u], tu[u]);
+            if (in)
+                a.applied[iu[u]] = ap ? 1 : 0;
+            const unsigned long long m = __ballot(ap);
+            if (m) {
+                n_applied += (unsigned long long)__popcll(m);
+                last = __shfl(iu[u], 63 - __clzll((long long)m), WAVE);
+            }
+        }
+    }
+    if (lane == 0) {
+        t.applied += n_applied;
+        t.ignored += len - n_applied;
+        wbt_seg_out(a, s, last, t);
+    }
+}
+
+/* segments longer than lane_max: a wave each.  A wave looks at 64 segments
+ * at a time, one per lane, and takes the long ones among them in turn. */
+__global__ void __launch_bounds__(BLOCK) k_wbt_walk_wave(TtArgs a)
+{
+    __shared__ unsigned long long s_red[TR_WORDS];
+    TtTally t;
+    const int lane = threadIdx.x & (WAVE - 1);
+    const uint64_t ns = a.red[TR_NSEG];
+    const uint64_t n_waves = (gridDim.x * (uint64_t)blockDim.x) / WAVE;
+    for (uint64_t c = (blockIdx.x * (uint64_t)blockDim.x + threadIdx.x) / WAVE; c * WAVE < ns;
+         c += n_waves) {
+        const uint64_t s = c * WAVE + lane;
+        const bool is_long = s < ns && a.seg_start[s + 1] - a.seg_start[s] > a.lane_max;
+        unsigned long long m = __ballot(is_long);
+        while (m) {
+            const int l = __ffsll((long long)m) - 1;
+            m &= m - 1;
+            wbt_seg_wave(a, c * WAVE + l, lane, t);
+        }
+    }
+    wbt_tally_flush(t, s_red, a.red);
+}
+
+/* the output rows: segment s with an applied op becomes row orank[s].  sk,
+ * 0-based okoff/ovoff (n_out+1 entries) and the per-row source addresses the
+ * chunk copies read.  fk / fv != 0: the offset is row x stride; else kpos /
+ * vpos hold it. */
+__global__ void __launch_bounds__(BLOCK)
+    k_wbt_scatter(TtArgs a, const uint64_t *orank, const uint64_t *kpos, const uint64_t *vpos,
+                  uint64_t seq_floor, uint64_t n_out, uint64_t kbytes, uint64_t vbytes,
+                  uint64_t fk, uint64_t fv, uint64_t *okoff, uint64_t *ovoff, uint64_t *osk,
+                  uint64_t *row_ksrc, uint64_t *row_vsrc)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        okoff[n_out] = kbytes;
+        ovoff[n_out] = vbytes;
+    }
+    const uint64_t ns = a.red[TR_NSEG];
+    for (uint64_t s = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; s < ns;
+         s += gridDim.x * (uint64_t)blockDim.x) {
+        if (!a.seg_has[s])
+            continue;
+        const uint64_t r = orank[s];
+        const uint32_t i = a.seg_last[s];
+        if (r >= n_out || i >= a.n)
+            continue; /* cannot happen: the totals come from the same columns */
+        osk[r] = ((seq_floor + i) << 1) | (uint64_t)(a.flags[i] & TT_OP_DELETE);
+        okoff[r] = fk ? r * fk : kpos[s];
+        ovoff[r] = fv ? r * fv : vpos[s];
+        uint64_t kl;
+        row_ksrc[r] = (uint64_t)wb_key(a.k, i, &kl);
+        row_vsrc[r] = (uint64_t)(a.svals + a.svoff[i]);
+    }
+}
+
+/* head flags (the incr batch's kernel).  d_red: TR_WORDS u64 words,
+ * initialised here; launch_psum and launch_incr_segs follow. */
+void launch_wbt_heads(const WbKeys &k, uint64_t n, const uint64_t *d_w, const uint32_t *d_ix,
+                      uint64_t *d_head, uint64_t *d_red, hipStream_t s)
+{
+    uint64_t init[TR_WORDS];
+    for (int j = 0; j < TR_WORDS; j++)
+        init[j] = (j == TR_KMIN || j == TR_VMIN || j == TR_PVMIN) ? ~0ull : 0ull;
+    HIP_CHECK(hipMemcpyAsync(d_red, init, sizeof(init), hipMemcpyHostToDevice, s));
+    k_incr_heads<<<grid_for(n, BLOCK), BLOCK, 0, s>>>(k, n, d_w, d_ix, d_head);
+}
+
+/* both walk kernels; the segment count is read on the device, so the grids
+ * are sized by the op count, which bounds it */
+void launch_wbt_walk(const TtArgs &a, hipStream_t s)
+{
+    k_wbt_walk_lane<<<grid_for(a.n, BLOCK), BLOCK, 0, s>>>(a);
+    /* at most n / lane_max segments are long, and a wave takes one at a time */
+    k_wbt_walk_wave<<<grid_for((a.n / (a.lane_max + 1ull) + 1) * WAVE, BLOCK), BLOCK, 0, s>>>(a);
+}
+
+void launch_wbt_scatter(const TtArgs &a, uint64_t n_seg, const uint64_t *d_orank,
+                        const uint64_t *d_kpos, const uint64_t *d_vpos, uint64_t seq_floor,
+                        uint64_t n_out, uint64_t kbytes, uint64_t vbytes, uint64_t fk, uint64_t fv,
+                        uint64_t *d_okoff, uint64_t *d_ovoff, uint64_t *d_osk,
+                        uint64_t *d_row_ksrc, uint64_t *d_row_vsrc, hipStream_t s)
+{
+    k_wbt_scatter<<<grid_for(n_seg, BLOCK), BLOCK, 0, s>>>(a, d_orank, d_kpos, d_vpos, seq_floor,
+                                                          n_out, kbytes, vbytes, fk, fv, d_okoff,
+                                                          d_ovoff, d_osk, d_row_ksrc, d_row_vsrc);
+}

@@ -8,11 +8,14 @@
  * rebuilt: for every PUT the value header of the handle's data version (what
  * rrdb_put writes: [0x82 for v2][expire_ts BE][timetag 0 for v1/v2]) followed
  * by the user bytes; a remove contributes nothing, so its staged span is empty
- * whatever its val_offs span says.
+ * whatever its val_offs span says.  rrdb_write_batch_timetag stages the same
+ * layout with the op's timetag in the header (wb_stage_values_tt).
  */
 #pragma once
 #include <stdint.h>
 #include <string.h>
+
+#include "tt_verify.h"
 
 #define WB_MAX_OPS 0x7FFFFFFFull /* the sort carries the op index in 32 bits */
 
@@ -97,23 +100,28 @@ static inline bool wb_staged_bytes(uint64_t n, const uint64_t *val_offs, const u
     return true;
 }
 
-/* write the staged value blob (wb_staged_bytes long) and its n+1 offsets.
- * expire_ts may be null (all zero).  Input must have passed wb_validate. */
-static inline void wb_stage_values(uint64_t n, const uint8_t *values, const uint64_t *val_offs,
-                                   const uint32_t *expire_ts, const uint8_t *kinds,
-                                   uint32_t data_version, uint32_t default_ttl,
-                                   uint32_t epoch_now, uint8_t *out_vals, uint64_t *out_voff)
+/* write the staged value blob (wb_staged_bytes long) and its n+1 offsets, with
+ * timetags[i] big-endian in the 8 timetag bytes of every PUT header (data
+ * version 1 and 2; version 0 has none).  expire_ts, timetags and verify may be
+ * null (all zero).  out_flags, when not null, receives every op folded to the
+ * TT_OP_* bits the conflict rule reads (tt_verify.h).  Input must have passed
+ * wb_validate. */
+static inline void wb_stage_values_tt(uint64_t n, const uint8_t *values, const uint64_t *val_offs,
+                                      const uint32_t *expire_ts, const uint8_t *kinds,
+                                      const uint64_t *timetags, const uint8_t *verify,
+                                      uint32_t data_version, uint32_t default_ttl,
+                                      uint32_t epoch_now, uint8_t *out_vals, uint64_t *out_voff,
+                                      uint8_t *out_flags)
 {
     const uint32_t hdr = wb_hdr_len(data_version);
     const uint32_t off = data_version == 2 ? 1 : 0;
     uint64_t pos = 0;
     out_voff[0] = 0;
     for (uint64_t i = 0; i < n; i++) {
+        uint32_t ts = 0;
         if (kinds[i] == 0) {
-            uint32_t ts = expire_ts ? expire_ts[i] : 0;
             /* write-time default_ttl, as rrdb_put */
-            if (ts == 0 && default_ttl != 0)
-                ts = epoch_now + default_ttl;
+            ts = tt_stored_expire(expire_ts ? expire_ts[i] : 0, default_ttl, epoch_now);
             uint8_t *v = out_vals + pos;
             memset(v, 0, hdr);
             if (data_version == 2)
@@ -122,11 +130,27 @@ static inline void wb_stage_values(uint64_t n, const uint8_t *values, const uint
             v[off + 1] = (uint8_t)(ts >> 16);
             v[off + 2] = (uint8_t)(ts >> 8);
             v[off + 3] = (uint8_t)ts;
+            if (timetags && data_version >= 1)
+                for (int j = 0; j < 8; j++)
+                    v[off + 4 + j] = (uint8_t)(timetags[i] >> (8 * (7 - j)));
             const uint64_t vl = val_offs[i + 1] - val_offs[i];
             if (vl)
                 memcpy(v + hdr, values + val_offs[i], vl);
             pos += hdr + vl;
         }
+        if (out_flags)
+            out_flags[i] = tt_op_flags(kinds[i], verify && verify[i] != 0, ts, epoch_now,
+                                       data_version);
         out_voff[i + 1] = pos;
     }
+}
+
+/* the same with timetag 0 everywhere: what rrdb_write_batch stages */
+static inline void wb_stage_values(uint64_t n, const uint8_t *values, const uint64_t *val_offs,
+                                   const uint32_t *expire_ts, const uint8_t *kinds,
+                                   uint32_t data_version, uint32_t default_ttl,
+                                   uint32_t epoch_now, uint8_t *out_vals, uint64_t *out_voff)
+{
+    wb_stage_values_tt(n, values, val_offs, expire_ts, kinds, nullptr, nullptr, data_version,
+                       default_ttl, epoch_now, out_vals, out_voff, nullptr);
 }

@@ -4,7 +4,9 @@ entry point on one handle — writes, batched writes (rrdb_write_batch, which
 the oracle replays through put/remove), batched counter increments
 (rrdb_incr_batch, which the oracle replays through get/ttl/put), batched
 check-and-mutate ops (rrdb_check_and_mutate_batch, which the oracle replays
-through get/ttl and the applied puts/removes), flushes, point/range/batched reads with
+through get/ttl and the applied puts/removes), batched writes with timetags
+(rrdb_write_batch_timetag, whose run the oracle ingests from a model), flushes,
+point/range/batched reads with
 the serving lanes forced on, pipelined count scans, paged scans, real
 compactions, checkpoints and restores — cross-checked against the CPU
 oracle driven with the same operation stream.  Complements tools/soak.py
@@ -136,6 +138,44 @@ def replay_cas(o, ops, now):
     return errors, exists, values
 
 
+def replay_timetag(o, ops, now, ckpt_dir, decree):
+    """the batch on the oracle: no read returns a timetag, so the ops of this
+    kind write theirs into the user bytes as well (b"t<timetag>:..."; no other
+    writer's value starts with a t, and those store timetag 0).  The bases are
+    read first, the ops walked by the rule of the header comment, and the
+    model's run is ingested with seqnos from the oracle's own floor, which a
+    checkpoint (it flushes, as the batch does) reports."""
+    assert o.checkpoint(ckpt_dir, decree) == OK
+    floor = None
+    for line in open(os.path.join(ckpt_dir, "checkpoint.%d" % decree, "MANIFEST")):
+        f = line.split()
+        if f and f[0] == "next_seq_floor":
+            floor = int(f[1])
+    live = {}
+    for k in {op[0] for op in ops}:
+        e, val = o.get(k, now)
+        if e == OK:
+            live[k] = int(val[1:val.index(b":")]) if val.startswith(b"t") else 0
+    applied, newest = [], {}
+    for i, (k, v, ets, tt, verify) in enumerate(ops):
+        if v is None:
+            live.pop(k, None)
+            newest[k] = (b"", floor + i, 1)
+        else:
+            if verify and k in live and live[k] >= tt:
+                applied.append(0)
+                continue
+            if 0 < ets <= now:
+                live.pop(k, None)
+            else:
+                live[k] = tt
+            newest[k] = (D.encode_value(v, ets, tt, 1), floor + i, 0)
+        applied.append(1)
+    if newest:
+        o.ingest_run([(k,) + newest[k] for k in sorted(newest)])
+    return applied
+
+
 def main():
     steps = int(sys.argv[1]) if len(sys.argv) > 1 else 600
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 11
@@ -154,8 +194,26 @@ def main():
     tmp_o = tempfile.mkdtemp(prefix="stress_ckpt_o_")
     decree = 0
     for step in range(steps):
-        op = rnd.randrange(13)
-        if op == 12:  # batched check-and-mutate: every check type, lists of up
+        op = rnd.randrange(14)
+        if op == 13:  # batched writes with timetags: local and duplicated puts
+            # and removes on the shared key space, a past expire now and then
+            ops = []
+            for _ in range(rnd.choice([1, 7, 300, 2049, 5000])):
+                k = D.generate_key(b"hk%03d" % rnd.randrange(70), b"s%02d" % rnd.randrange(7))
+                tt = rnd.randrange(0, 40)
+                if rnd.random() < 0.15:
+                    ops.append((k, None, 0, 0, 0))
+                else:
+                    ops.append((k, b"t%d:%d" % (tt, step), rnd.choice([0, 0, 0, now + 50, now - 1]),
+                                tt, rnd.random() < 0.7))
+            decree += 1
+            err, applied, st = g.write_batch_timetag(ops, now)
+            assert err == OK and st.input_ops == len(ops)
+            assert applied == replay_timetag(o, ops, now, tmp_o, decree)
+            assert st.applied == sum(applied)
+            assert g.num_runs() == o.num_runs() and g.num_records() == o.num_records()
+            checks += 1
+        elif op == 12:  # batched check-and-mutate: every check type, lists of up
             # to three mutations on the check key's hashkey, now and then a
             # malformed op (an empty list, a check type out of range)
             ops = []
