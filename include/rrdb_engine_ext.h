@@ -304,7 +304,7 @@
  * means one kernel can tell it ran that kernel.
  *   - rank: RRDB_ROUTE_RANK_GLOBAL / _LDS / _LDST / _GRP, numbered as
  *     engine.rank_mode numbers them.  A mode that does not apply (lds with a
- *     non-chunked emit or a single run; ldst or grp on runs that are not
+ *     non-chunked emit, a single run or more than 64 runs; ldst or grp on runs that are not
  *     tail-word eligible; grp with more than 32 runs or the input-major
  *     emit) falls to ldst when engine.rank_mode is ldst and the runs are
  *     eligible, else to global.
@@ -320,6 +320,38 @@
  *   - Manual, window and auto passes all report.  A call that is rejected
  *     before the pass starts leaves the previous report.  Recording costs no
  *     device work and changes no behaviour.
+ *
+ * Multi_get lane.  A range multi_get is served by one device function behind
+ * several lanes, each with its own request and response plumbing, and which
+ * lane runs is decided per call: from the envs "engine.mg_persist" and
+ * "engine.mg_graph", the run count, the request size, and whether a lane came
+ * up at all (a refused graph capture or a resident kernel that is slow to
+ * start switches that lane off for the handle, silently).  Every lane returns
+ * the same rows; rrdb_last_multi_get_lane reports which one the last call
+ * took, so that a test or a benchmark that means one lane can tell it ran
+ * that lane.
+ *   - lane, for the last rrdb_multi_get: RRDB_MG_LANE_POINT_LIST (n_sort_keys
+ *     > 0), _SERVER (the resident mailbox kernel), _GRAPH (the captured
+ *     graph), _SMALL (the plain fused launch) or _GENERAL (the view path).
+ *     RRDB_MG_LANE_NONE: no call yet, or the call returned before any lane
+ *     (rejected arguments, a failed flush, an empty range).
+ *   - fused_first: when lane is _GENERAL, the fused lane (_SERVER, _GRAPH or
+ *     _SMALL) that ran first and handed the request back: more than 4096
+ *     candidate rows, a sortkey or user data above 65535 bytes, or a response
+ *     that does not fit the fused buffer.  _NONE when the general path was
+ *     taken directly (no run, or more than 64 runs).
+ *   - tail_read: 1 when the fused response was larger than the pinned prefix
+ *     that comes back with the header, so that the host read the whole
+ *     response from device memory in a second copy.
+ *   - batch_fused / batch_fallback, for the last rrdb_multi_get_batch: the
+ *     requests the batch kernel answered and those that went through the
+ *     per-request path (their sum is n_req).  batch_device_out: 1 when the
+ *     result was delivered in dev_vals / dev_val_offs.  All zero when the
+ *     batch was rejected.
+ *   - The two calls keep separate fields: a batch leaves lane, fused_first
+ *     and tail_read as the last rrdb_multi_get set them (its per-request
+ *     fallbacks do not report), and rrdb_multi_get leaves the batch fields.
+ *     Recording costs no device work and changes no behaviour.
  */
 #ifndef RRDB_ENGINE_EXT_H
 #define RRDB_ENGINE_EXT_H
@@ -501,6 +533,29 @@ typedef struct {
 /* The rank and emit kernels the handle's last compaction pass dispatched to;
  * see the header comment.  Read-only.  kInvalidArgument: out == NULL. */
 int32_t rrdb_last_compact_route(void *h, rrdb_compact_route *out);
+
+enum {
+    RRDB_MG_LANE_NONE = 0,
+    RRDB_MG_LANE_POINT_LIST = 1, /* n_sort_keys > 0: the batched-get core   */
+    RRDB_MG_LANE_SERVER = 2,     /* resident mailbox kernel                 */
+    RRDB_MG_LANE_GRAPH = 3,      /* captured graph                          */
+    RRDB_MG_LANE_SMALL = 4,      /* plain fused launch                      */
+    RRDB_MG_LANE_GENERAL = 5     /* view build + host limiter               */
+};
+
+typedef struct {
+    int32_t lane;             /* RRDB_MG_LANE_*: what answered the last rrdb_multi_get */
+    int32_t fused_first;      /* the fused lane that ran first and handed back, or _NONE */
+    int32_t tail_read;        /* 1 = the response needed the second device read */
+    int32_t batch_device_out; /* 1 = the last batch was delivered on the device */
+    uint64_t batch_fused;     /* requests of the last batch the kernel answered */
+    uint64_t batch_fallback;  /* requests of the last batch served one by one   */
+} rrdb_multi_get_lane;
+
+/* The lane the handle's last rrdb_multi_get took and the fused / fallback
+ * split of its last rrdb_multi_get_batch; see the header comment.  Read-only.
+ * kInvalidArgument: out == NULL. */
+int32_t rrdb_last_multi_get_lane(void *h, rrdb_multi_get_lane *out);
 
 #ifdef __cplusplus
 }

@@ -197,6 +197,27 @@ ROUTE_RANK_GLOBAL, ROUTE_RANK_LDS, ROUTE_RANK_LDST, ROUTE_RANK_GRP = 0, 1, 3, 4
 ROUTE_EMIT_RANK, ROUTE_EMIT_INPUT, ROUTE_EMIT_CHUNKED, ROUTE_EMIT_CHUNKED_FIXED = 0, 1, 2, 3
 
 
+class _MultiGetLane(C.Structure):
+    _fields_ = [("lane", C.c_int32), ("fused_first", C.c_int32), ("tail_read", C.c_int32),
+                ("batch_device_out", C.c_int32), ("batch_fused", C.c_uint64),
+                ("batch_fallback", C.c_uint64)]
+
+
+# rrdb_multi_get_lane values (include/rrdb_engine_ext.h)
+MG_LANE_NONE, MG_LANE_POINT_LIST, MG_LANE_SERVER, MG_LANE_GRAPH, MG_LANE_SMALL, \
+    MG_LANE_GENERAL = 0, 1, 2, 3, 4, 5
+
+
+@dataclass
+class MultiGetLane:
+    lane: int = 0
+    fused_first: int = 0
+    tail_read: int = 0
+    batch_device_out: int = 0
+    batch_fused: int = 0
+    batch_fallback: int = 0
+
+
 @dataclass
 class IncrBatchStats:
     input_ops: int = 0
@@ -426,6 +447,10 @@ class RrdbLib:
         if self.has_compact_route:
             L.rrdb_last_compact_route.restype = C.c_int32
             L.rrdb_last_compact_route.argtypes = [C.c_void_p, C.POINTER(_CompactRoute)]
+        self.has_multi_get_lane = hasattr(L, "rrdb_last_multi_get_lane")
+        if self.has_multi_get_lane:
+            L.rrdb_last_multi_get_lane.restype = C.c_int32
+            L.rrdb_last_multi_get_lane.argtypes = [C.c_void_p, C.POINTER(_MultiGetLane)]
 
     @property
     def backend(self) -> str:
@@ -825,6 +850,22 @@ class RrdbPartition:
         if err != OK:
             raise RuntimeError(f"rrdb_last_compact_route failed: status {err}")
         return rt.rank, rt.emit
+
+    # ---- multi_get lane: engine-only (include/rrdb_engine_ext.h) ----
+    def last_multi_get_lane(self) -> MultiGetLane:
+        """Which serving lane the last multi_get on this handle took (the
+        MG_LANE_* values), whether a fused lane handed it back first, whether
+        the response needed the second device read, and the fused / fallback
+        split of the last multi_get_batch."""
+        if not self.lib.has_multi_get_lane:
+            raise RuntimeError(
+                f"last_multi_get_lane: backend {self.lib.backend!r} ({self.lib.path}) does not "
+                "export rrdb_last_multi_get_lane (engine-only extension)")
+        ln = _MultiGetLane()
+        err = self._L.rrdb_last_multi_get_lane(self._h, C.byref(ln))
+        if err != OK:
+            raise RuntimeError(f"rrdb_last_multi_get_lane failed: status {err}")
+        return MultiGetLane(**{f[0]: getattr(ln, f[0]) for f in _MultiGetLane._fields_})
 
     # ---- partition split: engine-only (include/rrdb_engine_ext.h) ----
     def split(self, child: "RrdbPartition", new_partition_count: int):

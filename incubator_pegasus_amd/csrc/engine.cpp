@@ -968,6 +968,11 @@ struct HipEngine {
        (rrdb_last_compact_route): written at the branches of compact_begin /
        compact_finish, read by nothing else */
     rrdb_compact_route last_route{RRDB_ROUTE_NONE, RRDB_ROUTE_NONE};
+    /* which lane the last rrdb_multi_get took and how the last
+       rrdb_multi_get_batch split (rrdb_last_multi_get_lane): written at the
+       branches of multi_get_locked / rrdb_multi_get_batch, read by nothing
+       else */
+    rrdb_multi_get_lane last_mg_lane{};
     int split_crc_lds = 1; /* rrdb_split classify: crc64 table staged in LDS
                               once per workgroup (1, default) or read from
                               global memory (0) (env "engine.split_crc":
@@ -2640,9 +2645,14 @@ static bool valid_beyond(HipEngine *e, const std::string &bound, bool reverse)
 }
 
 static int32_t multi_get_locked(void *h, const rrdb_multi_get_request *q, uint32_t epoch_now,
-                                rrdb_result *out)
+                                rrdb_result *out, rrdb_multi_get_lane *rep)
 {
     auto *e = (HipEngine *)h;
+    /* rep: the lane report of this call (a batch's per-request fallbacks
+     * hand in a scratch one); only ever written */
+    rep->lane = RRDB_MG_LANE_NONE;
+    rep->fused_first = RRDB_MG_LANE_NONE;
+    rep->tail_read = 0;
     if (engine_flush(e) != RRDB_OK) {
         result_init(out);
         out->error = RRDB_IO_ERROR;
@@ -2666,6 +2676,7 @@ static int32_t multi_get_locked(void *h, const rrdb_multi_get_request *q, uint32
 
     if (q->n_sort_keys > 0) {
         /* point-list variant (on_multi_get:779-860) over the batched-get core */
+        rep->lane = RRDB_MG_LANE_POINT_LIST;
         std::vector<uint64_t> offs(q->n_sort_keys + 1);
         std::string keys;
         for (uint64_t i = 0; i < q->n_sort_keys; i++) {
@@ -2753,6 +2764,7 @@ static int32_t multi_get_locked(void *h, const rrdb_multi_get_request *q, uint32
         const uint8_t *d_blob = nullptr;
         const uint8_t *h_resp = e->mg_hout;
         bool served = false;
+        int32_t fused_lane = RRDB_MG_LANE_SMALL;
         if (sizeof(MgGraphHdr) + in_n <= MG_GRAPH_IN && e->mg_persist_wanted() &&
             e->server_ready()) {
             /* resident-kernel lane: write the request slice, bump the
@@ -2812,6 +2824,7 @@ static int32_t multi_get_locked(void *h, const rrdb_multi_get_request *q, uint32
                 h_resp = e->mg_mb->resp;
                 d_blob = e->mg_dout + 32;
                 served = true;
+                fused_lane = RRDB_MG_LANE_SERVER;
             }
         }
         if (!served && sizeof(MgGraphHdr) + in_n <= MG_GRAPH_IN && e->mg_graph_ready()) {
@@ -2842,6 +2855,7 @@ static int32_t multi_get_locked(void *h, const rrdb_multi_get_request *q, uint32
             spin_sync(e->stream);
             d_blob = e->mg_dout + 32;
             served = true;
+            fused_lane = RRDB_MG_LANE_GRAPH;
         }
         if (!served && in_n <= HipEngine::MG_IN_CAP) {
             uint64_t o = 0;
@@ -2889,6 +2903,7 @@ static int32_t multi_get_locked(void *h, const rrdb_multi_get_request *q, uint32
         }
         const int64_t *hdr4 = (const int64_t *)h_resp;
         if (hdr4[0] >= 0) {
+            rep->lane = fused_lane;
             uint64_t m = (uint64_t)hdr4[0];
             uint64_t kb = (uint64_t)hdr4[2], vb = (uint64_t)hdr4[3];
             int64_t complete_flag = hdr4[1];
@@ -2900,6 +2915,7 @@ static int32_t multi_get_locked(void *h, const rrdb_multi_get_request *q, uint32
                 if (blob_n <= HipEngine::MG_OUT_PREFIX) {
                     memcpy(hb, h_resp + 32, blob_n); /* already on host */
                 } else {
+                    rep->tail_read = 1;
                     HIP_OK(hipMemcpyAsync(hb, d_blob, blob_n, hipMemcpyDeviceToHost,
                                           e->stream));
                     HIP_OK(hipStreamSynchronize(e->stream));
@@ -2918,8 +2934,10 @@ static int32_t multi_get_locked(void *h, const rrdb_multi_get_request *q, uint32
             return out->error;
         }
         /* fallback: large range or oversize rows — general path below */
+        rep->fused_first = fused_lane;
     }
 
+    rep->lane = RRDB_MG_LANE_GENERAL;
     uint64_t *d_view = nullptr, n = 0;
     e->build_view(&start, &stop_excl, &d_view, &n);
     if (n == 0) {
@@ -3109,7 +3127,17 @@ int32_t rrdb_multi_get(void *h, const rrdb_multi_get_request *q, uint32_t epoch_
                        rrdb_result *out)
 {
     std::lock_guard<std::mutex> g(((HipEngine *)h)->mu);
-    return multi_get_locked(h, q, epoch_now, out);
+    return multi_get_locked(h, q, epoch_now, out, &((HipEngine *)h)->last_mg_lane);
+}
+
+int32_t rrdb_last_multi_get_lane(void *h, rrdb_multi_get_lane *out)
+{
+    if (!out)
+        return RRDB_INVALID_ARGUMENT;
+    auto *e = (HipEngine *)h;
+    std::lock_guard<std::mutex> g(e->mu);
+    *out = e->last_mg_lane;
+    return RRDB_OK;
 }
 
 /* phase 1 of the compaction (the pipelined-partitions seam; the reference
@@ -3216,8 +3244,10 @@ static int32_t compact_begin(HipEngine *e, const rrdb_compact_options *opts, uin
      * blockIdx&7; legacy kernels add to bank 0; finish sums all banks */
     CompactStatsDev *d_stats = e->talloc<CompactStatsDev>(8 * sizeof(CompactStatsDev));
     HIP_OK(hipMemsetAsync(d_stats, 0, 8 * sizeof(CompactStatsDev), e->stream));
-    if (e->rank_mode == 1 && R > 1 && emit_mode == 2) {
-        /* LDS-staged block rank: shift-8 bound table + per-run block counts */
+    if (e->rank_mode == 1 && R > 1 && R <= RRDB_MAX_RUNS && emit_mode == 2) {
+        /* LDS-staged block rank: shift-8 bound table + per-run block counts.
+         * The kernel keeps per-run window tables of RRDB_MAX_RUNS entries in
+         * LDS; more runs than that take the global rank below */
         e->last_route.rank = RRDB_ROUTE_RANK_LDS;
         uint64_t *d_bt8_off = nullptr, *d_bt8 = nullptr;
         {
@@ -5260,6 +5290,9 @@ extern "C" int32_t rrdb_multi_get_batch(void *h, uint64_t n_req, const uint8_t *
     e->server_quit_sync();
     e->scratch_reset();
     Arena *a = result_init(out);
+    e->last_mg_lane.batch_fused = 0;
+    e->last_mg_lane.batch_fallback = 0;
+    e->last_mg_lane.batch_device_out = 0;
     if (shared->n_sort_keys != 0 || shared->sort_key_filter_type < 0 ||
         shared->sort_key_filter_type > 3) {
         out->error = RRDB_INVALID_ARGUMENT;
@@ -5268,12 +5301,13 @@ extern "C" int32_t rrdb_multi_get_batch(void *h, uint64_t n_req, const uint8_t *
     out->group_counts = (uint64_t *)a->alloc(n_req * 8);
     out->group_errors = (int32_t *)a->alloc(n_req * 4);
     /* fused batch only covers the full-range shape (no sortkey bounds, no
-     * range-clamping prefix filter); others run per-request */
+     * range-clamping prefix filter) over at most RRDB_MAX_RUNS runs (mg_core
+     * indexes per-run LDS arrays of that size); others run per-request */
     bool fused_ok = shared->start_sortkey.len == 0 && shared->stop_sortkey.len == 0 &&
                     shared->start_inclusive &&
                     !(shared->sort_key_filter_type == RRDB_FT_MATCH_PREFIX &&
                       shared->sort_key_filter_pattern.len > 0) &&
-                    !e->runs.empty();
+                    !e->runs.empty() && (int)e->runs.size() <= RRDB_MAX_RUNS;
     const uint64_t BLOB_STRIDE = 64 << 10;
     std::vector<int64_t> hdrs(n_req * 4, -1);
     uint8_t *d_blobs = nullptr;
@@ -5346,6 +5380,8 @@ extern "C" int32_t rrdb_multi_get_batch(void *h, uint64_t n_req, const uint8_t *
             }
             out->dev_vals = d_packed;
             out->dev_val_offs = d_poff_out;
+            e->last_mg_lane.batch_fused = n_req;
+            e->last_mg_lane.batch_device_out = 1;
             a->dev_ptrs.insert(a->dev_ptrs.end(), {(void *)d_packed, (void *)d_poff_out});
             out->count = rows;
             out->error = RRDB_OK;
@@ -5367,13 +5403,16 @@ extern "C" int32_t rrdb_multi_get_batch(void *h, uint64_t n_req, const uint8_t *
     for (uint64_t i = 0; i < n_req; i++) {
         if (hdrs[i * 4] >= 0) {
             total_rows += (uint64_t)hdrs[i * 4];
+            e->last_mg_lane.batch_fused++;
         } else {
+            e->last_mg_lane.batch_fallback++;
             /* general path per request (rare) */
             is_fb[i] = 1;
             rrdb_multi_get_request req = *shared;
             req.hash_key.data = hash_keys + hk_offs[i];
             req.hash_key.len = hk_offs[i + 1] - hk_offs[i];
-            multi_get_locked(h, &req, epoch_now, &fb[i]);
+            rrdb_multi_get_lane scratch_rep;
+            multi_get_locked(h, &req, epoch_now, &fb[i], &scratch_rep);
             total_rows += fb[i].count;
         }
     }

@@ -49,6 +49,20 @@ def test_hip_lib_refuses_cpu_only_open():
     assert lib.rrdb_open(1, 0, 0) in (None, 0)
 
 
+def test_multi_get_lane_entry_point_is_engine_only(oracle_part):
+    """rrdb_last_multi_get_lane lives in the extension header: the engine
+    exports it, the oracle does not, and the binding says so."""
+    ext = open(os.path.join(REPO, "include", "rrdb_engine_ext.h")).read()
+    assert re.search(r"\bint32_t\s+rrdb_last_multi_get_lane\s*\(\s*void\s*\*h,\s*"
+                     r"rrdb_multi_get_lane\s*\*out\s*\)", ext)
+    assert "rrdb_last_multi_get_lane" not in open(HEADER).read()
+    assert not oracle_part.lib.has_multi_get_lane
+    with pytest.raises(RuntimeError, match="rrdb_last_multi_get_lane"):
+        oracle_part.last_multi_get_lane()
+    if os.path.exists(HIP_SO):
+        assert hasattr(ctypes.CDLL(HIP_SO), "rrdb_last_multi_get_lane")
+
+
 def test_backend_strings():
     lib = ctypes.CDLL(ORACLE_SO)
     lib.rrdb_backend.restype = ctypes.c_char_p
