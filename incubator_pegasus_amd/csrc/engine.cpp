@@ -27,6 +27,7 @@
 #include "../../include/rrdb_engine.h"
 #include "../../include/rrdb_engine_ext.h"
 #include "engine_common.h"
+#include "emit_tile.h"
 #include "wb_stage.h"
 #include "cas_stage.h"
 
@@ -114,8 +115,13 @@ void launch_emit_compact_chunked(const DevRun *, const uint64_t *, uint64_t, con
                                  const uint64_t *, const uint64_t *, uint32_t, uint64_t,
                                  uint64_t, uint64_t, uint64_t *, uint64_t *, uint32_t *,
                                  uint32_t *, uint8_t *, uint8_t *, uint64_t *, uint64_t *,
-                                 uint64_t *, uint64_t *, uint64_t *,
-                                 uint64_t, uint64_t, hipStream_t);
+                                 uint64_t *, uint64_t *, uint64_t *, hipStream_t);
+void launch_keep_tile_scan(const uint64_t *, uint64_t, uint32_t *, uint64_t *, uint64_t *,
+                           hipStream_t);
+void launch_emit_fixed_fused(const DevRun *, const uint64_t *, uint64_t, const uint64_t *,
+                             const uint64_t *, const uint8_t *, const uint32_t *, uint32_t,
+                             uint32_t, uint32_t, uint64_t, uint8_t *, uint8_t *, uint64_t *,
+                             uint64_t *, uint64_t *, hipStream_t);
 void launch_emit_compact(const DevRun *, const uint64_t *, uint64_t, const uint64_t *,
                          const uint8_t *, const uint32_t *, const uint64_t *, const uint64_t *,
                          const uint64_t *, uint32_t, uint8_t *, uint8_t *, uint64_t *, uint64_t *,
@@ -728,9 +734,10 @@ struct HipEngine {
         uint8_t *d_changed = nullptr;
         uint32_t *d_new_expire = nullptr;
         uint64_t *d_kpos = nullptr, *d_koffs = nullptr, *d_voffs = nullptr;
+        uint64_t *d_tile_base = nullptr; /* all-fixed-stride emit: first output row per tile */
         uint64_t *d_rank_of = nullptr;
         CompactStatsDev *d_stats = nullptr;
-        uint64_t fk = 0, fv = 0; /* all-fixed-stride emit (ksz/vsz skipped) */
+        uint32_t fk = 0, fv = 0; /* all-fixed-stride emit (ksz/vsz/kpos skipped) */
         bool no_rewrite = false;  /* changed/new_expire arrays skipped */
         /* the emit the arrays above were built for: engine.emit_mode as
          * phase 1 read it (chunked for a window), so that a set_envs between
@@ -3185,17 +3192,20 @@ static int32_t compact_begin(HipEngine *e, const rrdb_compact_options *opts, uin
     /* run ids in order[] are relative to this pointer, i.e. to the window */
     DevRun *dr = e->dev_runs() + first;
     /* full-range rank merge */
-    std::vector<uint64_t> lo(R, 0), hi(R), wprefix(R + 1);
+    std::vector<uint64_t> lo(R, 0), hi(R);
+    /* lo | hi | wprefix travel as one upload: [R] [R] [R + 1] */
+    std::vector<uint64_t> bounds(3 * (size_t)R + 1, 0);
     uint64_t acc = 0;
     for (int r = 0; r < R; r++) {
         hi[r] = wr[r].n;
-        wprefix[r] = acc;
+        bounds[R + r] = hi[r];
+        bounds[2 * R + r] = acc;
         acc += wr[r].n;
     }
-    wprefix[R] = acc;
-    uint64_t *d_lo = (uint64_t *)e->upload_tmp(lo.data(), R * 8);
-    uint64_t *d_hi = (uint64_t *)e->upload_tmp(hi.data(), R * 8);
-    uint64_t *d_wp = (uint64_t *)e->upload_tmp(wprefix.data(), (R + 1) * 8);
+    bounds[3 * R] = acc;
+    uint64_t *d_lo = (uint64_t *)e->upload_tmp(bounds.data(), bounds.size() * 8);
+    uint64_t *d_hi = d_lo + R;
+    uint64_t *d_wp = d_hi + R;
     uint64_t *d_order = e->talloc<uint64_t>(total * 8);
     e->resolve_phase_events(); /* previous pass's timing, before reuse */
     e->tev_have_emit = false;
@@ -3226,6 +3236,9 @@ static int32_t compact_begin(HipEngine *e, const rrdb_compact_options *opts, uin
     /* a non-bottommost output can hold tombstones (kept or converted), whose
      * rows are not fv long: it always takes the per-row-size path */
     bool fixed_emit = ffk > 0 && ffv > 0 && emit_mode == 2 && bottommost;
+    /* the fused emit indexes inside a tile in 32 bits */
+    if (ffk > EMIT_MAX_STRIDE || ffv > EMIT_MAX_STRIDE)
+        fixed_emit = false;
     /* no default-TTL and no user ops => the filter can never rewrite a
      * value: skip the changed/new_expire arrays and the patch pass.  Not so
      * when non-bottommost: an expired PUT is rewritten into a tombstone and
@@ -3236,7 +3249,13 @@ static int32_t compact_begin(HipEngine *e, const rrdb_compact_options *opts, uin
     uint64_t *d_ksz = fixed_emit ? nullptr : e->talloc<uint64_t>(total * 8);
     uint64_t *d_vsz = fixed_emit ? nullptr : e->talloc<uint64_t>(total * 8);
     uint64_t *d_keepw = e->talloc<uint64_t>(total * 8);
-    uint64_t *d_kpos = e->talloc<uint64_t>(total * 8);
+    /* all-fixed-stride: the emit scans the keep flags itself, tile by tile;
+     * only the per-tile counts are summed here */
+    uint64_t *d_kpos = fixed_emit ? nullptr : e->talloc<uint64_t>(total * 8);
+    const uint64_t n_tiles = emit_n_tiles(total);
+    uint32_t *d_tile_cnt = fixed_emit ? e->talloc<uint32_t>(n_tiles * 4) : nullptr;
+    uint64_t *d_tile_base = fixed_emit ? e->talloc<uint64_t>(n_tiles * 8) : nullptr;
+    uint64_t *d_n_out = fixed_emit ? e->talloc<uint64_t>(8) : nullptr;
     uint64_t *d_koffs = fixed_emit ? nullptr : e->talloc<uint64_t>(total * 8);
     uint64_t *d_voffs = fixed_emit ? nullptr : e->talloc<uint64_t>(total * 8);
     uint64_t *d_rank_of = emit_mode == 1 ? e->talloc<uint64_t>(total * 8) : nullptr;
@@ -3305,8 +3324,10 @@ static int32_t compact_begin(HipEngine *e, const rrdb_compact_options *opts, uin
         HIP_OK(hipHostMalloc((void **)&e->pend_stats_h, 8 * sizeof(CompactStatsDev)));
     HIP_OK(hipMemcpyAsync(e->pend_stats_h, d_stats, 8 * sizeof(CompactStatsDev),
                           hipMemcpyDeviceToHost, e->stream));
-    launch_psum(d_keepw, d_kpos, total, e->psum_scratch(total), e->stream);
-    if (!fixed_emit) {
+    if (fixed_emit) {
+        launch_keep_tile_scan(d_keepw, total, d_tile_cnt, d_tile_base, d_n_out, e->stream);
+    } else {
+        launch_psum(d_keepw, d_kpos, total, e->psum_scratch(total), e->stream);
         launch_psum(d_ksz, d_koffs, total, e->psum_scratch(total), e->stream);
         launch_psum(d_vsz, d_voffs, total, e->psum_scratch(total), e->stream);
     }
@@ -3314,9 +3335,12 @@ static int32_t compact_begin(HipEngine *e, const rrdb_compact_options *opts, uin
         HIP_OK(hipHostMalloc((void **)&e->pend_sizes, 6 * 8));
     uint64_t *t = e->pend_sizes;
     memset(t, 0, 6 * 8);
-    HIP_OK(hipMemcpyAsync(&t[0], d_kpos + total - 1, 8, hipMemcpyDeviceToHost, e->stream));
-    HIP_OK(hipMemcpyAsync(&t[1], d_keepw + total - 1, 8, hipMemcpyDeviceToHost, e->stream));
-    if (!fixed_emit) {
+    if (fixed_emit) {
+        /* the scan's grand total is the whole keep count: t[1] stays 0 */
+        HIP_OK(hipMemcpyAsync(&t[0], d_n_out, 8, hipMemcpyDeviceToHost, e->stream));
+    } else {
+        HIP_OK(hipMemcpyAsync(&t[0], d_kpos + total - 1, 8, hipMemcpyDeviceToHost, e->stream));
+        HIP_OK(hipMemcpyAsync(&t[1], d_keepw + total - 1, 8, hipMemcpyDeviceToHost, e->stream));
         HIP_OK(hipMemcpyAsync(&t[2], d_koffs + total - 1, 8, hipMemcpyDeviceToHost, e->stream));
         HIP_OK(hipMemcpyAsync(&t[3], d_ksz + total - 1, 8, hipMemcpyDeviceToHost, e->stream));
         HIP_OK(hipMemcpyAsync(&t[4], d_voffs + total - 1, 8, hipMemcpyDeviceToHost, e->stream));
@@ -3341,8 +3365,9 @@ static int32_t compact_begin(HipEngine *e, const rrdb_compact_options *opts, uin
     e->pend.d_voffs = d_voffs;
     e->pend.d_rank_of = d_rank_of;
     e->pend.d_stats = d_stats;
-    e->pend.fk = fixed_emit ? ffk : 0;
-    e->pend.fv = fixed_emit ? ffv : 0;
+    e->pend.d_tile_base = d_tile_base;
+    e->pend.fk = fixed_emit ? (uint32_t)ffk : 0;
+    e->pend.fv = fixed_emit ? (uint32_t)ffv : 0;
     e->pend.no_rewrite = no_rewrite;
     for (int i = 0; i < 6; i++)
         e->pend.ev[i] = ev[i];
@@ -3432,9 +3457,15 @@ static int32_t compact_finish(HipEngine *e, rrdb_compact_stats *stats)
         e->alloc_base(nr, n_out, kbytes, vbytes, keep_inputs ? RunAlloc::Arena : RunAlloc::Abort);
         HIP_OK(hipEventRecord(ev[3], e->stream));
         /* fk and no_rewrite imply the chunked emit (compact_begin) */
-        if (e->pend.emit_mode == 2) {
-            e->last_route.emit =
-                e->pend.fk ? RRDB_ROUTE_EMIT_CHUNKED_FIXED : RRDB_ROUTE_EMIT_CHUNKED;
+        if (e->pend.fk) {
+            /* all-fixed-stride: scan, row columns and both copies in one
+             * kernel over the tiles compact_begin counted */
+            e->last_route.emit = RRDB_ROUTE_EMIT_CHUNKED_FIXED;
+            launch_emit_fixed_fused(dr, d_order, total, d_keepw, e->pend.d_tile_base, d_changed,
+                                    d_new_expire, e->data_version, e->pend.fk, e->pend.fv, n_out,
+                                    nr.keys, nr.vals, nr.koff, nr.voff, nr.sk, e->stream);
+        } else if (e->pend.emit_mode == 2) {
+            e->last_route.emit = RRDB_ROUTE_EMIT_CHUNKED;
             uint64_t *d_row_ksrc = e->talloc<uint64_t>(n_out * 8);
             uint64_t *d_row_vsrc = e->talloc<uint64_t>(n_out * 8);
             uint32_t *d_row_patch = e->talloc<uint32_t>(n_out * 4);
@@ -3447,8 +3478,7 @@ static int32_t compact_finish(HipEngine *e, rrdb_compact_stats *stats)
                                         d_kpos, d_koffs, d_voffs, e->data_version, n_out, kbytes,
                                         vbytes, d_row_ksrc, d_row_vsrc, d_row_patch,
                                         d_row_expire, nr.keys, nr.vals, nr.koff, nr.voff, nr.sk,
-                                        d_kanchor, d_vanchor, e->pend.fk, e->pend.fv,
-                                        e->stream);
+                                        d_kanchor, d_vanchor, e->stream);
         } else if (e->pend.emit_mode == 1) {
             e->last_route.emit = RRDB_ROUTE_EMIT_INPUT;
             launch_emit_compact_inmajor(dr, R, d_wp, total, d_rank_of, d_keepw, d_changed,

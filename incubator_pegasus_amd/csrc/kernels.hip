@@ -20,9 +20,10 @@
  *  - disposition tallies accumulate in per-thread registers and flush once
  *    per block into 8 stat banks (shared-counter atomics serialized at
  *    ~88 adds/us and floored every fused kernel before)
- *  - emits: direct-indexed 16B-chunk copies for 16B-aligned fixed strides,
- *    row-per-thread u64 copies for other fixed strides, chunk-anchor
- *    binary-search copies for variable layouts
+ *  - emits: all-fixed-stride passes scan, build rows and copy in one kernel
+ *    per 1024-rank tile (k_emit_fixed_fused: direct-indexed 16B chunks for
+ *    16B-aligned strides, row-per-thread u64 pieces for the others);
+ *    chunk-anchor binary-search copies for variable layouts
  *  - serving: cooperative p-ary bounds + hashkey-prefix blooms in the fused
  *    multi_get; a hipGraph-captured lane and a persistent mailbox-polled
  *    1-workgroup server (bounded 2ms idle exit) remove the per-call
@@ -36,6 +37,7 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include "emit_tile.h"
 #include "engine_common.h"
 
 #define WAVE 64
@@ -2054,18 +2056,16 @@ __global__ void k_emit_compact(const DevRun *runs, const uint64_t *order, uint64
 
 /* chunked emit (the fast path, measured 2.8 TB/s on the probe vs 1.1 for
  * wave-per-record): one scatter pass builds output-row metadata, then pure
- * 16B-chunk-parallel copies with an offset binary search per chunk. */
-/* fk/fv nonzero = all-fixed-stride mode: row offsets and source addresses
- * derive from the keep count, so the per-rank ksz/vsz arrays and two of the
- * three full-length prefix sums are never built */
+ * 16B-chunk-parallel copies with an offset binary search per chunk.  The
+ * all-fixed-stride case never comes here: it has its own fused emit
+ * (k_emit_fixed_fused below). */
 __global__ void k_compact_gather_meta(const DevRun *runs, const uint64_t *order, uint64_t m,
                                       const uint64_t *keepw, const uint8_t *changed,
                                       const uint32_t *new_expire, const uint64_t *kpos,
                                       const uint64_t *koffs, const uint64_t *voffs,
                                       uint64_t *row_koff, uint64_t *row_voff, uint64_t *row_ksrc,
                                       uint64_t *row_vsrc, uint32_t *row_patch, uint64_t *osk,
-                                      uint64_t n_out, uint64_t kbytes, uint64_t vbytes,
-                                      uint64_t fk, uint64_t fv)
+                                      uint64_t n_out, uint64_t kbytes, uint64_t vbytes)
 {
     for (uint64_t p = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; p < m;
          p += gridDim.x * (uint64_t)blockDim.x) {
@@ -2075,11 +2075,9 @@ __global__ void k_compact_gather_meta(const DevRun *runs, const uint64_t *order,
         uint64_t id = order[p];
         const DevRun &r = runs[id >> 40];
         uint64_t i = id & 0xFFFFFFFFFFull;
-        row_koff[o] = fk ? o * fk : koffs[p];
-        row_voff[o] = fk ? o * fv : voffs[p];
-        row_ksrc[o] = (uint64_t)(fk ? r.keys + i * fk : r.keys + r.koff[i]);
-        /* input offsets stay voff-addressed: tombstones make input value
-         * strides irregular even when every PUT shares one length */
+        row_koff[o] = koffs[p];
+        row_voff[o] = voffs[p];
+        row_ksrc[o] = (uint64_t)(r.keys + r.koff[i]);
         row_vsrc[o] = (uint64_t)(r.vals + r.voff[i]);
         row_patch[o] = (changed && changed[p] == CH_REWRITE) ? 3 : 0;
         /* a filter-removed PUT of a non-bottommost pass leaves as a tombstone:
@@ -2226,6 +2224,203 @@ __global__ void k_patch_expire(const uint64_t *row_voff, const uint32_t *row_exp
         v[1] = (uint8_t)(ts >> 16);
         v[2] = (uint8_t)(ts >> 8);
         v[3] = (uint8_t)ts;
+    }
+}
+
+/* ---- fused all-fixed-stride emit (indexing: emit_tile.h) ----
+ * With one key stride and one value stride the output offset of a row is its
+ * kept-rank times the stride, so nothing per-rank has to travel between the
+ * rank kernel and the copies but keepw[] and order[]: a count of the keep
+ * flags per tile of EMIT_TILE ranks, a one-workgroup exclusive scan of those
+ * counts, and one kernel that scans its tile, writes the row columns and
+ * copies the tile's contiguous key and value spans with the row source
+ * addresses parked in LDS.  No workgroup ever waits for another. */
+
+/* one wave per tile: keep flags summed by ballot */
+__global__ void __launch_bounds__(BLOCK)
+k_keep_tile_counts(const uint64_t *keepw, uint64_t m, uint64_t n_tiles, uint32_t *counts)
+{
+    const uint32_t lane = threadIdx.x % WAVE;
+    const uint64_t wave = (blockIdx.x * (uint64_t)blockDim.x + threadIdx.x) / WAVE;
+    const uint64_t nwaves = (gridDim.x * (uint64_t)blockDim.x) / WAVE;
+    for (uint64_t t = wave; t < n_tiles; t += nwaves) {
+        const uint64_t p0 = t * EMIT_TILE;
+        const uint32_t len = emit_tile_len(m, t);
+        uint32_t c = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < EMIT_TILE; j += WAVE) {
+            bool k = j + lane < len && keepw[p0 + j + lane] != 0;
+            c += (uint32_t)__popcll(__ballot(k));
+        }
+        if (lane == 0)
+            counts[t] = c;
+    }
+}
+
+/* ONE workgroup: exclusive scan of the tile counts, EMIT_SCAN_PASS per pass,
+ * the running total carried from pass to pass; the grand total is n_out */
+__global__ void __launch_bounds__(BLOCK)
+k_keep_tile_scan(const uint32_t *counts, uint64_t n_tiles, uint64_t *tile_base, uint64_t *total)
+{
+    static_assert(EMIT_SCAN_PASS == BLOCK, "one tile count per thread per pass");
+    __shared__ uint32_t s_wsum[BLOCK / WAVE];
+    const uint32_t lane = threadIdx.x % WAVE, wv = threadIdx.x / WAVE;
+    const uint64_t passes = emit_scan_passes(n_tiles);
+    uint64_t carry = 0;
+    for (uint64_t ps = 0; ps < passes; ps++) {
+        const uint64_t t = emit_scan_tile(ps, threadIdx.x);
+        const uint32_t c = t < n_tiles ? counts[t] : 0;
+        uint32_t inc = c;
+        for (uint32_t d = 1; d < WAVE; d <<= 1) {
+            uint32_t up = __shfl_up(inc, d);
+            if (lane >= d)
+                inc += up;
+        }
+        if (lane == WAVE - 1)
+            s_wsum[wv] = inc;
+        __syncthreads();
+        uint32_t wbase = 0, ptot = 0;
+        for (uint32_t w = 0; w < BLOCK / WAVE; w++) {
+            uint32_t s = s_wsum[w];
+            wbase += w < wv ? s : 0;
+            ptot += s;
+        }
+        if (t < n_tiles)
+            tile_base[t] = emit_scan_base(carry, wbase, inc - c);
+        carry = emit_scan_carry(carry, ptot);
+        __syncthreads(); /* s_wsum is rewritten by the next pass */
+    }
+    if (threadIdx.x == 0)
+        *total = carry;
+}
+
+/* copy a tile's contiguous output span of cnt rows; the source address of
+ * local row l is s_src[l].  PATCH: rows flagged in s_pat get s_exp[l] stored
+ * big-endian at byte hoff, in registers before the store (hoff + 4 <= 8, so
+ * the header lies in the row's first piece) */
+template <bool PATCH>
+__device__ static inline void emit_copy_span(uint8_t *dst, const uint64_t *s_src, uint32_t cnt,
+                                             uint32_t stride, const uint8_t *s_pat,
+                                             const uint32_t *s_exp, uint32_t hoff)
+{
+    if (emit_stride_chunked(stride)) {
+        const uint32_t cpr = emit_chunks_per_row(stride);
+        const uint32_t n_chunks = emit_span_chunks(cnt, stride);
+        for (uint32_t c = threadIdx.x; c < n_chunks; c += BLOCK) {
+            uint32_t row, off;
+            emit_chunk_row(c, cpr, &row, &off);
+            const uint8_t *src = (const uint8_t *)s_src[row] + off;
+            uint64_t w[2];
+            __builtin_memcpy(w, src, 16);
+            if (PATCH && off == 0 && s_pat[row])
+                w[0] = emit_patch_word(w[0], s_exp[row], hoff);
+            __builtin_memcpy(dst + ((uint64_t)c << 4), w, 16);
+        }
+    } else {
+        /* one thread copies one whole row in u64 pieces: consecutive threads
+         * write consecutive stride-length spans */
+        const uint32_t nw = emit_row_words(stride);
+        for (uint32_t row = threadIdx.x; row < cnt; row += BLOCK) {
+            const uint8_t *src = (const uint8_t *)s_src[row];
+            uint8_t *d = dst + (uint64_t)row * stride;
+            const bool pat = PATCH && s_pat[row];
+            const uint32_t ts = pat ? s_exp[row] : 0;
+            for (uint32_t q = 0; q < nw; q++) {
+                uint64_t w;
+                __builtin_memcpy(&w, src + 8 * q, 8);
+                if (pat && q == 0)
+                    w = emit_patch_word(w, ts, hoff);
+                __builtin_memcpy(d + 8 * q, &w, 8);
+            }
+            for (uint32_t b = 8 * nw; b < stride; b++)
+                d[b] = (pat && nw == 0) ? emit_patch_byte(src[b], b, ts, hoff) : src[b];
+        }
+    }
+}
+
+/* one workgroup per tile, grid-stride.  REWRITE: changed[]/new_expire[] are
+ * present and rewritten rows get their expire header patched in the copy */
+template <bool REWRITE>
+__global__ void __launch_bounds__(BLOCK)
+k_emit_fixed_fused(const DevRun *runs, const uint64_t *order, const uint64_t *keepw, uint64_t m,
+                   const uint64_t *tile_base, uint64_t n_tiles, const uint8_t *changed,
+                   const uint32_t *new_expire, uint32_t dv, uint32_t fk, uint32_t fv,
+                   uint64_t n_out, uint8_t *kout, uint8_t *vout, uint64_t *okoff,
+                   uint64_t *ovoff, uint64_t *osk)
+{
+    static_assert(EMIT_THREADS == BLOCK, "tile geometry follows the workgroup size");
+    constexpr uint32_t NW = BLOCK / WAVE;             /* waves */
+    constexpr uint32_t NS = EMIT_RANKS_PER_THREAD * NW; /* 64-rank segments per tile */
+    __shared__ uint64_t s_ksrc[EMIT_TILE];
+    __shared__ uint64_t s_vsrc[EMIT_TILE];
+    __shared__ uint32_t s_exp[REWRITE ? EMIT_TILE : 1];
+    __shared__ uint8_t s_pat[REWRITE ? EMIT_TILE : 1];
+    __shared__ uint32_t s_seg[NS];
+    const uint32_t tid = threadIdx.x, lane = tid % WAVE, wv = tid / WAVE;
+    const uint32_t hoff = emit_expire_off(dv);
+    for (uint64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+        const uint64_t p0 = t * EMIT_TILE;
+        const uint32_t len = emit_tile_len(m, t);
+        uint64_t id[EMIT_RANKS_PER_THREAD];
+        uint32_t below[EMIT_RANKS_PER_THREAD];
+        bool kp[EMIT_RANKS_PER_THREAD];
+#pragma unroll
+        for (uint32_t j = 0; j < EMIT_RANKS_PER_THREAD; j++) {
+            const uint32_t l = emit_tile_slot(tid, j);
+            const bool in = l < len;
+            const uint64_t kw = in ? keepw[p0 + l] : 0;
+            id[j] = in ? order[p0 + l] : 0;
+            kp[j] = kw != 0;
+            /* segment j*NW+wv holds in-tile ranks [64*(j*NW+wv), +64) */
+            const uint64_t b = __ballot(kp[j]);
+            below[j] = (uint32_t)__popcll(b & ((1ull << lane) - 1));
+            if (lane == 0)
+                s_seg[j * NW + wv] = (uint32_t)__popcll(b);
+        }
+        __syncthreads();
+        uint32_t pre[EMIT_RANKS_PER_THREAD] = {0, 0, 0, 0};
+        uint32_t cnt = 0;
+#pragma unroll
+        for (uint32_t q = 0; q < NS; q++) {
+            const uint32_t c = s_seg[q];
+#pragma unroll
+            for (uint32_t j = 0; j < EMIT_RANKS_PER_THREAD; j++)
+                pre[j] += q < j * NW + wv ? c : 0;
+            cnt += c;
+        }
+        const uint64_t base = tile_base[t];
+#pragma unroll
+        for (uint32_t j = 0; j < EMIT_RANKS_PER_THREAD; j++) {
+            if (!kp[j])
+                continue;
+            const uint32_t loc = pre[j] + below[j];
+            const uint64_t o = base + loc;
+            const DevRun &r = runs[id[j] >> 40];
+            const uint64_t i = id[j] & 0xFFFFFFFFFFull;
+            s_ksrc[loc] = (uint64_t)(r.keys + i * fk);
+            /* input offsets stay voff-addressed: tombstones make input value
+             * strides irregular even when every PUT shares one length */
+            s_vsrc[loc] = (uint64_t)(r.vals + r.voff[i]);
+            osk[o] = r.sk[i];
+            okoff[o] = emit_row_off(o, fk);
+            ovoff[o] = emit_row_off(o, fv);
+            if (REWRITE) {
+                const uint64_t p = p0 + emit_tile_slot(tid, j);
+                const bool ch = changed[p] == CH_REWRITE;
+                s_pat[loc] = ch ? 1 : 0;
+                s_exp[loc] = ch ? new_expire[p] : 0;
+            }
+        }
+        if (t == n_tiles - 1 && tid == 0) {
+            okoff[n_out] = emit_row_off(n_out, fk);
+            ovoff[n_out] = emit_row_off(n_out, fv);
+        }
+        __syncthreads();
+        emit_copy_span<REWRITE>(vout + emit_row_off(base, fv), s_vsrc, cnt, fv, s_pat, s_exp,
+                                hoff);
+        emit_copy_span<false>(kout + emit_row_off(base, fk), s_ksrc, cnt, fk, nullptr, nullptr,
+                              0);
+        __syncthreads(); /* the next tile overwrites the LDS tables */
     }
 }
 
@@ -2451,44 +2646,59 @@ void launch_emit_compact_chunked(const DevRun *d_runs, const uint64_t *d_order, 
                                  uint8_t *d_vout, uint64_t *d_okoff /* also the key row offsets */,
                                  uint64_t *d_ovoff /* also the value row offsets */,
                                  uint64_t *d_osk, uint64_t *d_kanchor, uint64_t *d_vanchor,
-                                 uint64_t fk, uint64_t fv, hipStream_t s)
+                                 hipStream_t s)
 {
     k_compact_gather_meta<<<grid_for(m, BLOCK), BLOCK, 0, s>>>(
         d_runs, d_order, m, d_keepw, d_changed, d_new_expire, d_kpos, d_koffs, d_voffs, d_okoff,
-        d_ovoff, d_row_ksrc, d_row_vsrc, d_row_patch, d_osk, n_out, kbytes, vbytes, fk, fv);
+        d_ovoff, d_row_ksrc, d_row_vsrc, d_row_patch, d_osk, n_out, kbytes, vbytes);
     if (d_changed)
         k_compact_gather_expire<<<grid_for(m, BLOCK), BLOCK, 0, s>>>(
             d_keepw, d_kpos, d_changed, d_new_expire, m, d_row_expire);
-    bool kfix = fk > 0 && (fk & 15) == 0, vfix = fk > 0 && (fv & 15) == 0;
-    if (kfix) {
-        k_copy_chunks_fixed<<<grid_for((kbytes + 15) >> 4, BLOCK), BLOCK, 0, s>>>(
-            d_row_ksrc, n_out, fk, d_kout);
-    } else if (fk > 0) {
-        k_copy_rows_fixed<<<grid_for(n_out, BLOCK), BLOCK, 0, s>>>(d_row_ksrc, n_out, fk,
-                                                                   d_kout);
-    } else {
-        uint64_t kanch = ((kbytes + 15) >> 4 >> 6) + 1;
-        k_chunk_anchors<<<grid_for(kanch, BLOCK), BLOCK, 0, s>>>(d_okoff, n_out, kanch,
-                                                                d_kanchor);
-        k_copy_chunks<<<grid_for((kbytes + 15) >> 4, BLOCK), BLOCK, 0, s>>>(
-            d_okoff, d_row_ksrc, n_out, kbytes, d_kanchor, kanch, d_kout);
-    }
-    if (vfix) {
-        k_copy_chunks_fixed<<<grid_for((vbytes + 15) >> 4, BLOCK), BLOCK, 0, s>>>(
-            d_row_vsrc, n_out, fv, d_vout);
-    } else if (fk > 0) {
-        k_copy_rows_fixed<<<grid_for(n_out, BLOCK), BLOCK, 0, s>>>(d_row_vsrc, n_out, fv,
-                                                                   d_vout);
-    } else {
-        uint64_t vanch = ((vbytes + 15) >> 4 >> 6) + 1;
-        k_chunk_anchors<<<grid_for(vanch, BLOCK), BLOCK, 0, s>>>(d_ovoff, n_out, vanch,
-                                                                d_vanchor);
-        k_copy_chunks<<<grid_for((vbytes + 15) >> 4, BLOCK), BLOCK, 0, s>>>(
-            d_ovoff, d_row_vsrc, n_out, vbytes, d_vanchor, vanch, d_vout);
-    }
+    uint64_t kanch = ((kbytes + 15) >> 4 >> 6) + 1;
+    k_chunk_anchors<<<grid_for(kanch, BLOCK), BLOCK, 0, s>>>(d_okoff, n_out, kanch, d_kanchor);
+    k_copy_chunks<<<grid_for((kbytes + 15) >> 4, BLOCK), BLOCK, 0, s>>>(
+        d_okoff, d_row_ksrc, n_out, kbytes, d_kanchor, kanch, d_kout);
+    uint64_t vanch = ((vbytes + 15) >> 4 >> 6) + 1;
+    k_chunk_anchors<<<grid_for(vanch, BLOCK), BLOCK, 0, s>>>(d_ovoff, n_out, vanch, d_vanchor);
+    k_copy_chunks<<<grid_for((vbytes + 15) >> 4, BLOCK), BLOCK, 0, s>>>(
+        d_ovoff, d_row_vsrc, n_out, vbytes, d_vanchor, vanch, d_vout);
     if (d_changed)
         k_patch_expire<<<grid_for(n_out, BLOCK), BLOCK, 0, s>>>(d_ovoff, d_row_expire, n_out,
                                                                 dv, d_vout);
+}
+
+/* all-fixed-stride route, first half (compact_begin): per-tile keep counts
+ * and their exclusive scan; *d_total receives the output row count */
+void launch_keep_tile_scan(const uint64_t *d_keepw, uint64_t m, uint32_t *d_tile_cnt,
+                           uint64_t *d_tile_base, uint64_t *d_total, hipStream_t s)
+{
+    const uint64_t n_tiles = emit_n_tiles(m);
+    k_keep_tile_counts<<<grid_for(n_tiles, BLOCK / WAVE), BLOCK, 0, s>>>(d_keepw, m, n_tiles,
+                                                                         d_tile_cnt);
+    k_keep_tile_scan<<<1, BLOCK, 0, s>>>(d_tile_cnt, n_tiles, d_tile_base, d_total);
+}
+
+/* second half (compact_finish, n_out > 0): the fused scan + row build + copy.
+ * d_changed / d_new_expire are null when the pass can rewrite nothing */
+void launch_emit_fixed_fused(const DevRun *d_runs, const uint64_t *d_order, uint64_t m,
+                             const uint64_t *d_keepw, const uint64_t *d_tile_base,
+                             const uint8_t *d_changed, const uint32_t *d_new_expire, uint32_t dv,
+                             uint32_t fk, uint32_t fv, uint64_t n_out, uint8_t *d_kout,
+                             uint8_t *d_vout, uint64_t *d_okoff, uint64_t *d_ovoff,
+                             uint64_t *d_osk, hipStream_t s)
+{
+    const uint64_t n_tiles = emit_n_tiles(m);
+    const uint32_t grid = (uint32_t)(n_tiles < (1ull << 20) ? n_tiles : (1ull << 20));
+    if (d_changed)
+        k_emit_fixed_fused<true><<<grid, BLOCK, 0, s>>>(d_runs, d_order, d_keepw, m, d_tile_base,
+                                                        n_tiles, d_changed, d_new_expire, dv, fk,
+                                                        fv, n_out, d_kout, d_vout, d_okoff,
+                                                        d_ovoff, d_osk);
+    else
+        k_emit_fixed_fused<false><<<grid, BLOCK, 0, s>>>(d_runs, d_order, d_keepw, m,
+                                                         d_tile_base, n_tiles, nullptr, nullptr,
+                                                         dv, fk, fv, n_out, d_kout, d_vout,
+                                                         d_okoff, d_ovoff, d_osk);
 }
 
 void launch_emit_compact_inmajor(const DevRun *d_runs, int R, const uint64_t *d_wprefix,
