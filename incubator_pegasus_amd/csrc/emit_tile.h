@@ -95,9 +95,51 @@ EMIT_HD static inline void emit_chunk_row(uint32_t c, uint32_t cpr, uint32_t *ro
     *off = (c - r * cpr) << 4;
 }
 
-/* other strides move one row per thread: u64 pieces, then single bytes */
+/* The chunk copy runs in batches: in a full batch every thread loads
+ * EMIT_COPY_DEPTH chunks, one workgroup width apart, before it stores the
+ * first, so that many 16-byte loads per lane are in flight.  The chunks past
+ * the last full batch are the remainder: one chunk per thread per step. */
+#ifndef EMIT_COPY_DEPTH
+#define EMIT_COPY_DEPTH 4u
+#endif
+#define EMIT_COPY_BATCH (EMIT_COPY_DEPTH * EMIT_THREADS) /* chunks per full batch */
+EMIT_HD static inline uint32_t emit_copy_full_batches(uint32_t n_chunks)
+{
+    return n_chunks / EMIT_COPY_BATCH;
+}
+/* chunk of thread tid's d-th load (d < EMIT_COPY_DEPTH) in full batch b */
+EMIT_HD static inline uint32_t emit_copy_chunk(uint32_t b, uint32_t d, uint32_t tid)
+{
+    return b * EMIT_COPY_BATCH + d * EMIT_THREADS + tid;
+}
+/* first chunk of the remainder; thread tid takes emit_copy_rem_start + tid,
+ * then steps by EMIT_THREADS while below n_chunks */
+EMIT_HD static inline uint32_t emit_copy_rem_start(uint32_t n_chunks)
+{
+    return emit_copy_full_batches(n_chunks) * EMIT_COPY_BATCH;
+}
+
+/* other strides move one row per thread: u64 pieces, then the tail (< 8
+ * bytes) as at most one 4-, one 2- and one 1-byte piece, in that order */
 EMIT_HD static inline uint32_t emit_row_words(uint32_t stride) { return stride >> 3; }
 EMIT_HD static inline uint32_t emit_row_tail(uint32_t stride) { return stride & 7u; }
+/* the row's words are loaded EMIT_ROW_WORD_BATCH at a time before they are
+ * stored; the tail pieces travel with the first batch */
+#define EMIT_ROW_WORD_BATCH 4u
+/* byte offset of the tail piece of `size` (4, 2 or 1) bytes; valid when
+ * emit_row_tail(stride) & size */
+EMIT_HD static inline uint32_t emit_row_tail_off(uint32_t stride, uint32_t size)
+{
+    const uint32_t tail = emit_row_tail(stride);
+    return 8 * emit_row_words(stride) + (tail & ~(2 * size - 1));
+}
+
+/* the emit kernel keeps every run's keys / vals / voff / sk pointers in LDS:
+ * one entry per run a handle can hold (RRDB_MAX_RUNS) */
+#define EMIT_RUN_TAB 64u
+/* order word -> run and row */
+EMIT_HD static inline uint32_t emit_order_run(uint64_t id) { return (uint32_t)(id >> 40); }
+EMIT_HD static inline uint64_t emit_order_row(uint64_t id) { return id & 0xFFFFFFFFFFull; }
 
 /* rewritten expire timestamp: 4 bytes big-endian at byte hoff of the value
  * (1 for data version 2, whose values start with a format byte; else 0) */

@@ -118,7 +118,7 @@ void launch_emit_compact_chunked(const DevRun *, const uint64_t *, uint64_t, con
                                  uint64_t *, uint64_t *, uint64_t *, hipStream_t);
 void launch_keep_tile_scan(const uint64_t *, uint64_t, uint32_t *, uint64_t *, uint64_t *,
                            hipStream_t);
-void launch_emit_fixed_fused(const DevRun *, const uint64_t *, uint64_t, const uint64_t *,
+void launch_emit_fixed_fused(const DevRun *, int, const uint64_t *, uint64_t, const uint64_t *,
                              const uint64_t *, const uint8_t *, const uint32_t *, uint32_t,
                              uint32_t, uint32_t, uint64_t, uint8_t *, uint8_t *, uint64_t *,
                              uint64_t *, uint64_t *, hipStream_t);
@@ -3461,9 +3461,10 @@ static int32_t compact_finish(HipEngine *e, rrdb_compact_stats *stats)
             /* all-fixed-stride: scan, row columns and both copies in one
              * kernel over the tiles compact_begin counted */
             e->last_route.emit = RRDB_ROUTE_EMIT_CHUNKED_FIXED;
-            launch_emit_fixed_fused(dr, d_order, total, d_keepw, e->pend.d_tile_base, d_changed,
-                                    d_new_expire, e->data_version, e->pend.fk, e->pend.fv, n_out,
-                                    nr.keys, nr.vals, nr.koff, nr.voff, nr.sk, e->stream);
+            launch_emit_fixed_fused(dr, R, d_order, total, d_keepw, e->pend.d_tile_base,
+                                    d_changed, d_new_expire, e->data_version, e->pend.fk,
+                                    e->pend.fv, n_out, nr.keys, nr.vals, nr.koff, nr.voff, nr.sk,
+                                    e->stream);
         } else if (e->pend.emit_mode == 2) {
             e->last_route.emit = RRDB_ROUTE_EMIT_CHUNKED;
             uint64_t *d_row_ksrc = e->talloc<uint64_t>(n_out * 8);

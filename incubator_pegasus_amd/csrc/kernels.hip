@@ -38,6 +38,7 @@
 #include <stdio.h>
 
 #include "emit_tile.h"
+#include "grp_stage.h"
 #include "engine_common.h"
 
 #define WAVE 64
@@ -72,6 +73,22 @@ static inline int grid_for(uint64_t n, int per_block)
 /* ================= crc64 (device) =================
  * Same polynomial/table construction as the reference crc.cpp:236-295 —
  * restated; table built on host (launchers.cpp) and copied here. */
+/* A read of global memory through an address that came out of LDS (a run
+ * table entry, a parked row address).  The compiler cannot tell such a
+ * pointer's address space and would emit a generic load, which also counts
+ * as an LDS access: every LDS read after it then waits for it, and a batch
+ * of loads degenerates into one round trip each.  Saying that the address
+ * is global memory makes it a global load, which waits on the vector-memory
+ * counter alone.  No alignment is assumed. */
+typedef const __attribute__((address_space(1))) uint8_t *dev_gptr;
+template <typename W>
+__device__ static inline W dev_gload(uint64_t addr)
+{
+    W w;
+    __builtin_memcpy(&w, (dev_gptr)addr, sizeof(W));
+    return w;
+}
+
 __device__ uint64_t d_crc64_table[256];
 
 __device__ static inline uint64_t dev_crc64(const uint8_t *p, uint64_t n)
@@ -1035,7 +1052,8 @@ enum { D_NONE = 0, D_KEEP, D_SHADOWED, D_TOMBSTONE, D_EXPIRED, D_FILTERED };
 __device__ static int dev_filter_disposition(const DevRun &r, uint64_t i, const CompactParams &cp,
                                              int shadow, uint8_t *changed_out,
                                              uint32_t *new_ts_out, uint64_t *kl_out,
-                                             uint64_t *vl_out, const uint64_t *mword)
+                                             uint64_t *vl_out, const uint64_t *mword,
+                                             bool want_vl)
 {
     *changed_out = 0;
     *new_ts_out = 0;
@@ -1057,8 +1075,11 @@ __device__ static int dev_filter_disposition(const DevRun &r, uint64_t i, const 
     }
     uint64_t kl =
         r.fixed_klen ? r.fixed_klen : (r.koff[i + 1] - r.koff[i]);
-    uint64_t vl =
-        r.fixed_vlen ? r.fixed_vlen : (r.voff[i + 1] - r.voff[i]);
+    /* the value length is a voff gather when the run has tombstones; a
+     * caller that stores no per-row sizes does not pay for it */
+    uint64_t vl = 0;
+    if (want_vl)
+        vl = r.fixed_vlen ? r.fixed_vlen : (r.voff[i + 1] - r.voff[i]);
     int drop = 0, value_changed = 0;
     uint32_t new_ts_val = 0;
     uint32_t eff_expire = expire_ts; /* value_view's expire after default-ttl */
@@ -1157,14 +1178,16 @@ __device__ static int dev_filter_disposition(const DevRun &r, uint64_t i, const 
 __device__ static inline int dev_disposition(const DevRun &r, uint64_t i, const CompactParams &cp,
                                              int shadow, uint8_t *changed_out,
                                              uint32_t *new_ts_out, uint64_t *kl_out,
-                                             uint64_t *vl_out, const uint64_t *mword = nullptr)
+                                             uint64_t *vl_out, const uint64_t *mword = nullptr,
+                                             bool want_vl = true)
 {
     int disp = dev_filter_disposition(r, i, cp, shadow, changed_out, new_ts_out, kl_out, vl_out,
-                                      mword);
+                                      mword, want_vl);
     if (!cp.bottommost && disp >= D_TOMBSTONE) {
         *kl_out = r.fixed_klen ? r.fixed_klen : (r.koff[i + 1] - r.koff[i]);
         if (disp == D_TOMBSTONE) {
-            *vl_out = r.fixed_vlen ? r.fixed_vlen : (r.voff[i + 1] - r.voff[i]);
+            if (want_vl)
+                *vl_out = r.fixed_vlen ? r.fixed_vlen : (r.voff[i + 1] - r.voff[i]);
         } else {
             *vl_out = 0;
             *changed_out = CH_TOMBSTONE;
@@ -1618,7 +1641,8 @@ __device__ static inline int dev_count_ok(const DevRun &r, uint64_t i, const Sca
 }
 
 /* per-element epilogue of the group rank: MODE 0 = compaction outputs,
- * MODE 1 = view (order + shadowed), MODE 2 = fused count (no arrays) */
+ * MODE 1 = view (order + shadowed), MODE 2 = fused count (no arrays).
+ * `runs` is the kernel's LDS copy of the run records. */
 template <int MODE>
 __device__ static inline int grp_epilogue(const DevRun *runs, int q, uint64_t i, int shadow,
                                           uint64_t rank, const CompactParams &cp,
@@ -1647,7 +1671,8 @@ __device__ static inline int grp_epilogue(const DevRun *runs, int q, uint64_t i,
     uint8_t ch;
     uint32_t nts;
     uint64_t okl, ovl;
-    int disp = dev_disposition(runs[q], i, cp, shadow, &ch, &nts, &okl, &ovl, smeta);
+    int disp = dev_disposition(runs[q], i, cp, shadow, &ch, &nts, &okl, &ovl, smeta,
+                               vsz != nullptr);
     keepw[rank] = dev_emitted(disp, cp);
     if (changed)
         changed[rank] = ch;
@@ -1679,7 +1704,7 @@ __global__ void __launch_bounds__(GRP_BLOCK, 6) k_rank_grp(
     CompactStatsDev *stats)
 {
     __shared__ uint64_t s_ta[GRP_CAP], s_tb[GRP_CAP]; /* tails ping-pong */
-    __shared__ uint16_t s_oa[GRP_CAP], s_ob[GRP_CAP]; /* (q<<12)|segpos */
+    __shared__ uint16_t s_oa[GRP_CAP], s_ob[GRP_CAP]; /* (q<<GRP_ORG_SHIFT)|segpos */
     /* staged disposition column — only the count mode pays its LDS */
     constexpr int MCAP = (MODE == 2) ? GRP_CAP : 1;
     __shared__ uint64_t s_meta[MCAP];
@@ -1690,6 +1715,33 @@ __global__ void __launch_bounds__(GRP_BLOCK, 6) k_rank_grp(
     __shared__ uint64_t s_base, s_gsize;
     __shared__ uint32_t s_bmask;
     __shared__ int s_nl, s_allmeta;
+    /* the run records and window starts, copied once per workgroup: staging,
+     * the boundary-tail read and the epilogue read these, so no group waits
+     * on a global load of a pointer or a stride before its data loads */
+    __shared__ DevRun s_run[LDST_MAXR];
+    __shared__ uint64_t s_lo[LDST_MAXR];
+    static_assert(sizeof(DevRun) % sizeof(uint64_t) == 0, "run records copy as words");
+    static_assert(GRP_BLOCK == GRP_STAGE_THREADS && GRP_CAP == GRP_STAGE_THREADS * GRP_STAGE_SLOTS,
+                  "staging geometry follows the workgroup and the group cap");
+
+    {
+        constexpr uint32_t RW = sizeof(DevRun) / sizeof(uint64_t);
+        const uint64_t *src = (const uint64_t *)runs;
+        uint64_t *dst = (uint64_t *)s_run;
+        for (uint32_t w = threadIdx.x; w < (uint32_t)R * RW; w += GRP_BLOCK)
+            dst[w] = src[w];
+        if (threadIdx.x < (unsigned)R)
+            s_lo[threadIdx.x] = lo[threadIdx.x];
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            int am = 1;
+            for (int q = 0; q < R; q++)
+                if (!s_run[q].meta)
+                    am = 0;
+            s_allmeta = am;
+        }
+        /* (published by the first group's barriers) */
+    }
 
     GrpTally tally;
     for (uint64_t g = blockIdx.x; g < n_groups; g += gridDim.x) {
@@ -1698,54 +1750,77 @@ __global__ void __launch_bounds__(GRP_BLOCK, 6) k_rank_grp(
             uint64_t a0 = anch[g * R + q], a1 = anch[(g + 1) * R + q];
             s_a0[q] = a0;
             s_seglen[q] = a1 - a0;
-            s_btail[q] = (a0 > lo[q]) ? runs[q].tails[a0 - 1] : 0;
+            s_btail[q] = (a0 > s_lo[q])
+                             ? dev_gload<uint64_t>((uint64_t)s_run[q].tails + 8 * (a0 - 1))
+                             : 0;
             if (q == 0)
                 s_bmask = 0;
         }
         __syncthreads();
         if (threadIdx.x < (unsigned)R) {
             int q = (int)threadIdx.x;
-            if (s_a0[q] > lo[q])
+            if (s_a0[q] > s_lo[q])
                 atomicOr(&s_bmask, 1u << q);
         }
         if (threadIdx.x == 0) {
             uint64_t t = 0, b = 0;
-            int am = 1;
             for (int q = 0; q < R; q++) {
                 s_segoff[q] = t;
                 s_loff[q] = t;
                 t += s_seglen[q];
-                b += s_a0[q] - lo[q];
-                if (!runs[q].meta)
-                    am = 0;
+                b += s_a0[q] - s_lo[q];
             }
             s_segoff[R] = t;
             s_loff[R] = t;
             s_gsize = t;
             s_base = b;
             s_nl = R;
-            s_allmeta = am;
         }
         __syncthreads();
         uint64_t gsize = s_gsize;
         bool staged = gsize <= GRP_CAP;
-        if (staged) {
-            /* stream each segment through LDS exactly once, org alongside */
-            for (int q = 0; q < R; q++) {
-                uint64_t len = s_seglen[q], off = s_segoff[q], a0 = s_a0[q];
-                const uint64_t *tq = runs[q].tails;
-                /* stage the disposition column only for the count mode:
-                 * compaction measured faster with direct gathers (the extra
-                 * 8KB LDS costs a workgroup of occupancy) */
-                const uint64_t *mq =
-                    (MODE == 2 && s_allmeta) ? runs[q].meta : nullptr;
-                for (uint64_t j = threadIdx.x; j < len; j += blockDim.x) {
-                    s_ta[off + j] = tq[a0 + j];
-                    s_oa[off + j] = (uint16_t)((q << GRP_ORG_SHIFT) | (uint32_t)j);
-                    if (mq)
-                        s_meta[off + j] = mq[a0 + j];
+        /* MODE 0 carries the group's meta words in registers across the
+         * merge rounds (slot k = staged position tid + 256 k) */
+        uint64_t mreg[GRP_STAGE_SLOTS];
+        const bool stage_meta = MODE != 1 && s_allmeta;
+        if (staged && gsize > 0) {
+            /* flat staging: every thread issues the tail (and meta) loads of
+             * all its positions, then writes them to LDS — one memory round
+             * trip per group instead of two per run.  Slots past the group
+             * load the group's last position and are not written. */
+            const uint32_t gs32 = (uint32_t)gsize;
+            const uint32_t nk =
+                (uint32_t)__builtin_amdgcn_readfirstlane((int)grp_stage_slots(gsize));
+            uint64_t treg[GRP_STAGE_SLOTS];
+            uint16_t oreg[GRP_STAGE_SLOTS];
+            uint32_t sq = 0;
+#pragma unroll
+            for (uint32_t k = 0; k < GRP_STAGE_SLOTS; k++) {
+                if (k < nk) {
+                    const uint32_t e = grp_stage_pos(threadIdx.x, k);
+                    const uint32_t ec = e < gs32 ? e : gs32 - 1;
+                    sq = grp_stage_seg(s_segoff, (uint32_t)R, ec, sq);
+                    const uint32_t j = ec - (uint32_t)s_segoff[sq];
+                    const uint64_t i = s_a0[sq] + j;
+                    treg[k] = dev_gload<uint64_t>((uint64_t)s_run[sq].tails + 8 * i);
+                    oreg[k] = (uint16_t)((sq << GRP_ORG_SHIFT) | j);
+                    if (stage_meta)
+                        mreg[k] = dev_gload<uint64_t>((uint64_t)s_run[sq].meta + 8 * i);
                 }
             }
+#pragma unroll
+            for (uint32_t k = 0; k < GRP_STAGE_SLOTS; k++) {
+                const uint32_t e = grp_stage_pos(threadIdx.x, k);
+                if (k < nk && e < gs32) {
+                    s_ta[e] = treg[k];
+                    s_oa[e] = oreg[k];
+                    /* the count mode stages the disposition column at once */
+                    if (MODE == 2 && stage_meta)
+                        s_meta[e] = mreg[k];
+                }
+            }
+        }
+        if (staged) {
             __syncthreads();
             /* pairwise merge rounds; ping-pong a->b->a->...  The list-offset
              * table ping-pongs too: the next round's offsets are a pure
@@ -1811,16 +1886,17 @@ __global__ void __launch_bounds__(GRP_BLOCK, 6) k_rank_grp(
             }
             const uint64_t *ft = cur ? s_tb : s_ta;
             const uint16_t *fo = cur ? s_ob : s_oa;
-            /* MODE 0: the retired ping-pong buffer stages the meta column
-             * (coalesced segment-major loads instead of per-element gathers
-             * in merged order) — costs no extra LDS */
+            /* MODE 0: the retired ping-pong buffer takes the meta column,
+             * segment-major as staged — costs no extra LDS, and the words
+             * were loaded with the tails, so nothing waits on memory here */
             uint64_t *s_mt = cur ? s_ta : s_tb;
-            if (MODE == 0 && s_allmeta) {
-                for (int q = 0; q < R; q++) {
-                    uint64_t len = s_seglen[q], off = s_segoff[q], a0 = s_a0[q];
-                    const uint64_t *mq = runs[q].meta;
-                    for (uint64_t j = threadIdx.x; j < len; j += blockDim.x)
-                        s_mt[off + j] = mq[a0 + j];
+            if (MODE == 0 && stage_meta) {
+                const uint32_t nk = grp_stage_slots(gsize);
+#pragma unroll
+                for (uint32_t k = 0; k < GRP_STAGE_SLOTS; k++) {
+                    const uint32_t e = grp_stage_pos(threadIdx.x, k);
+                    if (k < nk && e < gsize)
+                        s_mt[e] = mreg[k];
                 }
                 __syncthreads();
             }
@@ -1849,11 +1925,11 @@ __global__ void __launch_bounds__(GRP_BLOCK, 6) k_rank_grp(
                     }
                     uint64_t rank = s_base + p;
                     const uint64_t *sm = nullptr;
-                    if (MODE == 2 && s_allmeta)
+                    if (MODE == 2 && stage_meta)
                         sm = &s_meta[s_segoff[q] + (org & ((1u << GRP_ORG_SHIFT) - 1))];
-                    else if (MODE == 0 && s_allmeta)
+                    else if (MODE == 0 && stage_meta)
                         sm = &s_mt[s_segoff[q] + (org & ((1u << GRP_ORG_SHIFT) - 1))];
-                    disp = grp_epilogue<MODE>(runs, q, i, shadow, rank, cp, sp, order, keepw,
+                    disp = grp_epilogue<MODE>(s_run, q, i, shadow, rank, cp, sp, order, keepw,
                                               changed, new_expire, ksz, vsz, shadowed, sm);
                 }
                 if (MODE != 1)
@@ -1872,14 +1948,14 @@ __global__ void __launch_bounds__(GRP_BLOCK, 6) k_rank_grp(
                         q++;
                     uint64_t segpos = e - s_segoff[q];
                     uint64_t i = s_a0[q] + segpos;
-                    uint64_t myt = runs[q].tails[i];
+                    uint64_t myt = s_run[q].tails[i];
                     uint64_t lrank = segpos;
                     int shadow = 0;
                     uint32_t bm = s_bmask;
                     for (int p = 0; p < R; p++) {
                         if (p == q)
                             continue;
-                        const uint64_t *tp = runs[p].tails;
+                        const uint64_t *tp = s_run[p].tails;
                         uint64_t a0 = s_a0[p];
                         uint64_t l = a0, h = a0 + s_seglen[p];
                         if (p > q) {
@@ -1907,7 +1983,7 @@ __global__ void __launch_bounds__(GRP_BLOCK, 6) k_rank_grp(
                             shadow = 1;
                     }
                     uint64_t rank = s_base + lrank;
-                    disp = grp_epilogue<MODE>(runs, q, i, shadow, rank, cp, sp, order, keepw,
+                    disp = grp_epilogue<MODE>(s_run, q, i, shadow, rank, cp, sp, order, keepw,
                                               changed, new_expire, ksz, vsz, shadowed, nullptr);
                 }
                 if (MODE != 1)
@@ -2298,42 +2374,99 @@ k_keep_tile_scan(const uint32_t *counts, uint64_t n_tiles, uint64_t *tile_base, 
  * local row l is s_src[l].  PATCH: rows flagged in s_pat get s_exp[l] stored
  * big-endian at byte hoff, in registers before the store (hoff + 4 <= 8, so
  * the header lies in the row's first piece) */
+/* (the row source addresses are parked in LDS as integers: dev_gload) */
+struct EmitChunk {
+    uint64_t w[2];
+};
+
+template <bool PATCH>
+__device__ static inline EmitChunk emit_load_chunk(const uint64_t *s_src, uint32_t c,
+                                                   uint32_t cpr, const uint8_t *s_pat,
+                                                   const uint32_t *s_exp, uint32_t hoff)
+{
+    uint32_t row, off;
+    emit_chunk_row(c, cpr, &row, &off);
+    EmitChunk v = dev_gload<EmitChunk>(s_src[row] + off);
+    if (PATCH && off == 0 && s_pat[row])
+        v.w[0] = emit_patch_word(v.w[0], s_exp[row], hoff);
+    return v;
+}
+
 template <bool PATCH>
 __device__ static inline void emit_copy_span(uint8_t *dst, const uint64_t *s_src, uint32_t cnt,
                                              uint32_t stride, const uint8_t *s_pat,
                                              const uint32_t *s_exp, uint32_t hoff)
 {
+    const uint32_t tid = threadIdx.x;
     if (emit_stride_chunked(stride)) {
         const uint32_t cpr = emit_chunks_per_row(stride);
         const uint32_t n_chunks = emit_span_chunks(cnt, stride);
-        for (uint32_t c = threadIdx.x; c < n_chunks; c += BLOCK) {
-            uint32_t row, off;
-            emit_chunk_row(c, cpr, &row, &off);
-            const uint8_t *src = (const uint8_t *)s_src[row] + off;
-            uint64_t w[2];
-            __builtin_memcpy(w, src, 16);
-            if (PATCH && off == 0 && s_pat[row])
-                w[0] = emit_patch_word(w[0], s_exp[row], hoff);
-            __builtin_memcpy(dst + ((uint64_t)c << 4), w, 16);
+        /* full batches: EMIT_COPY_DEPTH chunk loads per thread in flight
+         * before the first store */
+        const uint32_t nb = emit_copy_full_batches(n_chunks);
+        for (uint32_t b = 0; b < nb; b++) {
+            EmitChunk v[EMIT_COPY_DEPTH];
+#pragma unroll
+            for (uint32_t d = 0; d < EMIT_COPY_DEPTH; d++)
+                v[d] = emit_load_chunk<PATCH>(s_src, emit_copy_chunk(b, d, tid), cpr, s_pat,
+                                              s_exp, hoff);
+#pragma unroll
+            for (uint32_t d = 0; d < EMIT_COPY_DEPTH; d++)
+                __builtin_memcpy(dst + ((uint64_t)emit_copy_chunk(b, d, tid) << 4), &v[d], 16);
+        }
+        for (uint32_t c = emit_copy_rem_start(n_chunks) + tid; c < n_chunks; c += EMIT_THREADS) {
+            const EmitChunk v = emit_load_chunk<PATCH>(s_src, c, cpr, s_pat, s_exp, hoff);
+            __builtin_memcpy(dst + ((uint64_t)c << 4), &v, 16);
         }
     } else {
-        /* one thread copies one whole row in u64 pieces: consecutive threads
-         * write consecutive stride-length spans */
-        const uint32_t nw = emit_row_words(stride);
-        for (uint32_t row = threadIdx.x; row < cnt; row += BLOCK) {
-            const uint8_t *src = (const uint8_t *)s_src[row];
+        /* one thread copies one whole row: consecutive threads write
+         * consecutive stride-length spans.  The tail pieces and the first
+         * EMIT_ROW_WORD_BATCH words are loaded before anything is stored
+         * (an 18-byte key is three loads, then three stores) */
+        const uint32_t nw = emit_row_words(stride), tail = emit_row_tail(stride);
+        const uint32_t o4 = emit_row_tail_off(stride, 4), o2 = emit_row_tail_off(stride, 2),
+                       o1 = emit_row_tail_off(stride, 1);
+        for (uint32_t row = tid; row < cnt; row += EMIT_THREADS) {
+            const uint64_t src = s_src[row];
             uint8_t *d = dst + (uint64_t)row * stride;
             const bool pat = PATCH && s_pat[row];
             const uint32_t ts = pat ? s_exp[row] : 0;
-            for (uint32_t q = 0; q < nw; q++) {
-                uint64_t w;
-                __builtin_memcpy(&w, src + 8 * q, 8);
-                if (pat && q == 0)
-                    w = emit_patch_word(w, ts, hoff);
-                __builtin_memcpy(d + 8 * q, &w, 8);
+            uint32_t t4 = 0;
+            uint16_t t2 = 0;
+            uint8_t t1 = 0;
+            if (tail & 4)
+                t4 = dev_gload<uint32_t>(src + o4);
+            if (tail & 2)
+                t2 = dev_gload<uint16_t>(src + o2);
+            if (tail & 1)
+                t1 = dev_gload<uint8_t>(src + o1);
+            for (uint32_t q0 = 0; q0 < nw; q0 += EMIT_ROW_WORD_BATCH) {
+                uint64_t w[EMIT_ROW_WORD_BATCH];
+#pragma unroll
+                for (uint32_t u = 0; u < EMIT_ROW_WORD_BATCH; u++)
+                    if (q0 + u < nw)
+                        w[u] = dev_gload<uint64_t>(src + 8 * (q0 + u));
+                if (pat && q0 == 0)
+                    w[0] = emit_patch_word(w[0], ts, hoff);
+#pragma unroll
+                for (uint32_t u = 0; u < EMIT_ROW_WORD_BATCH; u++)
+                    if (q0 + u < nw)
+                        __builtin_memcpy(d + 8 * (q0 + u), &w[u], 8);
             }
-            for (uint32_t b = 8 * nw; b < stride; b++)
-                d[b] = (pat && nw == 0) ? emit_patch_byte(src[b], b, ts, hoff) : src[b];
+            if (pat && nw == 0) {
+                /* a row shorter than one word: patch the tail pieces bytewise */
+                const uint64_t tw = ((uint64_t)t4 << (8 * o4)) | ((uint64_t)t2 << (8 * o2)) |
+                                    ((uint64_t)t1 << (8 * o1));
+                for (uint32_t b = 0; b < tail; b++)
+                    d[b] = emit_patch_byte((uint8_t)(tw >> (8 * b)), b, ts, hoff);
+                continue;
+            }
+            if (tail & 4)
+                __builtin_memcpy(d + o4, &t4, 4);
+            if (tail & 2)
+                __builtin_memcpy(d + o2, &t2, 2);
+            if (tail & 1)
+                d[o1] = t1;
         }
     }
 }
@@ -2341,8 +2474,9 @@ __device__ static inline void emit_copy_span(uint8_t *dst, const uint64_t *s_src
 /* one workgroup per tile, grid-stride.  REWRITE: changed[]/new_expire[] are
  * present and rewritten rows get their expire header patched in the copy */
 template <bool REWRITE>
-__global__ void __launch_bounds__(BLOCK)
-k_emit_fixed_fused(const DevRun *runs, const uint64_t *order, const uint64_t *keepw, uint64_t m,
+__global__ void __launch_bounds__(BLOCK, 6)
+k_emit_fixed_fused(const DevRun *runs, int R, const uint64_t *order, const uint64_t *keepw,
+                   uint64_t m,
                    const uint64_t *tile_base, uint64_t n_tiles, const uint8_t *changed,
                    const uint32_t *new_expire, uint32_t dv, uint32_t fk, uint32_t fv,
                    uint64_t n_out, uint8_t *kout, uint8_t *vout, uint64_t *okoff,
@@ -2356,64 +2490,107 @@ k_emit_fixed_fused(const DevRun *runs, const uint64_t *order, const uint64_t *ke
     __shared__ uint32_t s_exp[REWRITE ? EMIT_TILE : 1];
     __shared__ uint8_t s_pat[REWRITE ? EMIT_TILE : 1];
     __shared__ uint32_t s_seg[NS];
-    const uint32_t tid = threadIdx.x, lane = tid % WAVE, wv = tid / WAVE;
+    /* per-run pointers, filled once per workgroup (run of a rank: order >> 40) */
+    __shared__ uint64_t s_rkeys[EMIT_RUN_TAB], s_rvals[EMIT_RUN_TAB], s_rvoff[EMIT_RUN_TAB],
+        s_rsk[EMIT_RUN_TAB];
+    static_assert(EMIT_RUN_TAB >= RRDB_MAX_RUNS, "one table entry per run of a handle");
+    const uint32_t tid = threadIdx.x, lane = tid % WAVE;
+    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid / WAVE));
     const uint32_t hoff = emit_expire_off(dv);
+    if (tid < (uint32_t)R && tid < EMIT_RUN_TAB) {
+        s_rkeys[tid] = (uint64_t)runs[tid].keys;
+        s_rvals[tid] = (uint64_t)runs[tid].vals;
+        s_rvoff[tid] = (uint64_t)runs[tid].voff;
+        s_rsk[tid] = (uint64_t)runs[tid].sk;
+    }
+    if (blockIdx.x == 0 && tid == 0) { /* the terminal offsets */
+        okoff[n_out] = emit_row_off(n_out, fk);
+        ovoff[n_out] = emit_row_off(n_out, fv);
+    }
+    __syncthreads();
     for (uint64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
         const uint64_t p0 = t * EMIT_TILE;
         const uint32_t len = emit_tile_len(m, t);
-        uint64_t id[EMIT_RANKS_PER_THREAD];
-        uint32_t below[EMIT_RANKS_PER_THREAD];
+        uint64_t id[EMIT_RANKS_PER_THREAD], kw[EMIT_RANKS_PER_THREAD];
+        uint32_t below = 0; /* kept ranks below the slot in its segment: a byte per slot */
         bool kp[EMIT_RANKS_PER_THREAD];
+        uint8_t chg[EMIT_RANKS_PER_THREAD];
+        uint32_t nexp[EMIT_RANKS_PER_THREAD];
+        const uint64_t base = tile_base[t];
+        /* the tile's keep and order words in one batch: a slot past the tile
+         * reads the tile's first rank (always present) and is masked out */
 #pragma unroll
         for (uint32_t j = 0; j < EMIT_RANKS_PER_THREAD; j++) {
             const uint32_t l = emit_tile_slot(tid, j);
-            const bool in = l < len;
-            const uint64_t kw = in ? keepw[p0 + l] : 0;
-            id[j] = in ? order[p0 + l] : 0;
-            kp[j] = kw != 0;
+            const uint64_t p = p0 + (l < len ? l : 0);
+            kw[j] = keepw[p];
+            id[j] = order[p];
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < EMIT_RANKS_PER_THREAD; j++) {
+            kp[j] = emit_tile_slot(tid, j) < len && kw[j] != 0;
             /* segment j*NW+wv holds in-tile ranks [64*(j*NW+wv), +64) */
             const uint64_t b = __ballot(kp[j]);
-            below[j] = (uint32_t)__popcll(b & ((1ull << lane) - 1));
+            below |= (uint32_t)__popcll(b & ((1ull << lane) - 1)) << (8 * j);
             if (lane == 0)
                 s_seg[j * NW + wv] = (uint32_t)__popcll(b);
+        }
+        /* the gathers of all four slots are issued together, kept or not,
+         * ahead of the barrier and the segment scan: every slot holds a valid
+         * (run, row), so a dropped slot's loads are harmless and nothing
+         * branches before the loads are out */
+        uint64_t vo[EMIT_RANKS_PER_THREAD], skw[EMIT_RANKS_PER_THREAD];
+#pragma unroll
+        for (uint32_t j = 0; j < EMIT_RANKS_PER_THREAD; j++) {
+            const uint32_t q = emit_order_run(id[j]);
+            const uint64_t i = emit_order_row(id[j]);
+            /* input offsets stay voff-addressed: tombstones make input value
+             * strides irregular even when every PUT shares one length */
+            vo[j] = dev_gload<uint64_t>(s_rvoff[q] + 8 * i);
+            skw[j] = dev_gload<uint64_t>(s_rsk[q] + 8 * i);
         }
         __syncthreads();
         uint32_t pre[EMIT_RANKS_PER_THREAD] = {0, 0, 0, 0};
         uint32_t cnt = 0;
 #pragma unroll
         for (uint32_t q = 0; q < NS; q++) {
-            const uint32_t c = s_seg[q];
+            /* every lane reads the same count and a wave's segments are
+             * its own: the sums are scalar arithmetic */
+            const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_seg[q]);
 #pragma unroll
             for (uint32_t j = 0; j < EMIT_RANKS_PER_THREAD; j++)
                 pre[j] += q < j * NW + wv ? c : 0;
             cnt += c;
         }
-        const uint64_t base = tile_base[t];
+        if (REWRITE) {
+            /* the rewrite columns join the gathers in flight (coalesced,
+             * so they land with them); issued here to spare registers
+             * across the barrier */
+#pragma unroll
+            for (uint32_t j = 0; j < EMIT_RANKS_PER_THREAD; j++) {
+                const uint32_t l = emit_tile_slot(tid, j);
+                const uint64_t p = p0 + (l < len ? l : 0);
+                chg[j] = changed[p];
+                nexp[j] = new_expire[p];
+            }
+        }
 #pragma unroll
         for (uint32_t j = 0; j < EMIT_RANKS_PER_THREAD; j++) {
             if (!kp[j])
                 continue;
-            const uint32_t loc = pre[j] + below[j];
+            const uint32_t loc = pre[j] + ((below >> (8 * j)) & 0xFFu);
             const uint64_t o = base + loc;
-            const DevRun &r = runs[id[j] >> 40];
-            const uint64_t i = id[j] & 0xFFFFFFFFFFull;
-            s_ksrc[loc] = (uint64_t)(r.keys + i * fk);
-            /* input offsets stay voff-addressed: tombstones make input value
-             * strides irregular even when every PUT shares one length */
-            s_vsrc[loc] = (uint64_t)(r.vals + r.voff[i]);
-            osk[o] = r.sk[i];
+            const uint32_t q = emit_order_run(id[j]);
+            s_ksrc[loc] = s_rkeys[q] + emit_order_row(id[j]) * fk;
+            s_vsrc[loc] = s_rvals[q] + vo[j];
+            osk[o] = skw[j];
             okoff[o] = emit_row_off(o, fk);
             ovoff[o] = emit_row_off(o, fv);
             if (REWRITE) {
-                const uint64_t p = p0 + emit_tile_slot(tid, j);
-                const bool ch = changed[p] == CH_REWRITE;
+                const bool ch = chg[j] == CH_REWRITE;
                 s_pat[loc] = ch ? 1 : 0;
-                s_exp[loc] = ch ? new_expire[p] : 0;
+                s_exp[loc] = ch ? nexp[j] : 0;
             }
-        }
-        if (t == n_tiles - 1 && tid == 0) {
-            okoff[n_out] = emit_row_off(n_out, fk);
-            ovoff[n_out] = emit_row_off(n_out, fv);
         }
         __syncthreads();
         emit_copy_span<REWRITE>(vout + emit_row_off(base, fv), s_vsrc, cnt, fv, s_pat, s_exp,
@@ -2680,7 +2857,7 @@ void launch_keep_tile_scan(const uint64_t *d_keepw, uint64_t m, uint32_t *d_tile
 
 /* second half (compact_finish, n_out > 0): the fused scan + row build + copy.
  * d_changed / d_new_expire are null when the pass can rewrite nothing */
-void launch_emit_fixed_fused(const DevRun *d_runs, const uint64_t *d_order, uint64_t m,
+void launch_emit_fixed_fused(const DevRun *d_runs, int R, const uint64_t *d_order, uint64_t m,
                              const uint64_t *d_keepw, const uint64_t *d_tile_base,
                              const uint8_t *d_changed, const uint32_t *d_new_expire, uint32_t dv,
                              uint32_t fk, uint32_t fv, uint64_t n_out, uint8_t *d_kout,
@@ -2690,12 +2867,12 @@ void launch_emit_fixed_fused(const DevRun *d_runs, const uint64_t *d_order, uint
     const uint64_t n_tiles = emit_n_tiles(m);
     const uint32_t grid = (uint32_t)(n_tiles < (1ull << 20) ? n_tiles : (1ull << 20));
     if (d_changed)
-        k_emit_fixed_fused<true><<<grid, BLOCK, 0, s>>>(d_runs, d_order, d_keepw, m, d_tile_base,
-                                                        n_tiles, d_changed, d_new_expire, dv, fk,
-                                                        fv, n_out, d_kout, d_vout, d_okoff,
-                                                        d_ovoff, d_osk);
+        k_emit_fixed_fused<true><<<grid, BLOCK, 0, s>>>(d_runs, R, d_order, d_keepw, m,
+                                                        d_tile_base, n_tiles, d_changed,
+                                                        d_new_expire, dv, fk, fv, n_out, d_kout,
+                                                        d_vout, d_okoff, d_ovoff, d_osk);
     else
-        k_emit_fixed_fused<false><<<grid, BLOCK, 0, s>>>(d_runs, d_order, d_keepw, m,
+        k_emit_fixed_fused<false><<<grid, BLOCK, 0, s>>>(d_runs, R, d_order, d_keepw, m,
                                                          d_tile_base, n_tiles, nullptr, nullptr,
                                                          dv, fk, fv, n_out, d_kout, d_vout,
                                                          d_okoff, d_ovoff, d_osk);
