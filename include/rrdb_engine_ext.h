@@ -352,6 +352,37 @@
  *     and tail_read as the last rrdb_multi_get set them (its per-request
  *     fallbacks do not report), and rrdb_multi_get leaves the batch fields.
  *     Recording costs no device work and changes no behaviour.
+ *
+ * View route.  Every read that is no point lookup (rrdb_scan_open,
+ * rrdb_sortkey_count, the general lane of rrdb_multi_get) first builds a view:
+ * the records of every run inside the range are ranked into one order, and the
+ * newest versions that are no tombstone are gathered.  Which rank kernel runs
+ * is decided per view: from the env "engine.rank_mode", the run count, the key
+ * shape of the runs (as for the compaction route) and the number of records in
+ * the range.  Every kernel produces the same view; rrdb_last_view_route reports
+ * which one the last view took, so that a test that means one kernel can tell
+ * it ran that kernel.
+ *   - rank: RRDB_ROUTE_RANK_GRP (engine.rank_mode grp, at most 32 tail-word
+ *     eligible runs, more than one), _LDST (engine.rank_mode ldst on eligible
+ *     runs) or _GLOBAL (everything else: a single run, runs that are not
+ *     eligible, engine.rank_mode global or lds, which has no view kernel).
+ *     RRDB_ROUTE_NONE (-1): no view yet on the handle, no run, or no record of
+ *     any run inside the range; the other fields are 0 then.
+ *   - bound_levels: the _GLOBAL and _LDST kernels narrow their searches by a
+ *     bound table when there is more than one run and the range holds more
+ *     than 100000 records: 1, or 2 when the largest window of a run is long
+ *     enough for the coarse level (at least 9 << (engine.bt_shift + 6)
+ *     records).  0: no table; _LDST then searches global memory instead of
+ *     staging.  Always 0 under _GRP.
+ *   - n_groups: the anchor groups the _GRP kernel ranked, else 0.  Its grid is
+ *     capped at 3584 workgroups whatever engine.grp_blocks says, so above that
+ *     a workgroup ranks several groups.
+ *   - window_records: the records of all runs inside the range, shadowed
+ *     versions and tombstones included.  visible: the rows of the view.
+ *   - A read that returns before it builds a view (rejected arguments, a
+ *     failed flush, start beyond stop, a multi_get a fused lane answered, a
+ *     scan_next) leaves the previous report.  Recording costs no device work
+ *     and changes no behaviour.
  */
 #ifndef RRDB_ENGINE_EXT_H
 #define RRDB_ENGINE_EXT_H
@@ -556,6 +587,18 @@ typedef struct {
  * split of its last rrdb_multi_get_batch; see the header comment.  Read-only.
  * kInvalidArgument: out == NULL. */
 int32_t rrdb_last_multi_get_lane(void *h, rrdb_multi_get_lane *out);
+
+typedef struct {
+    int32_t rank;            /* RRDB_ROUTE_RANK_GLOBAL / _LDST / _GRP or RRDB_ROUTE_NONE */
+    int32_t bound_levels;    /* bound-table levels the rank searched through: 0, 1 or 2 */
+    uint64_t n_groups;       /* anchor groups of the group rank, else 0 */
+    uint64_t window_records; /* records of all runs inside the range */
+    uint64_t visible;        /* rows of the view: newest versions that are no tombstone */
+} rrdb_view_route;
+
+/* The rank kernel the handle's last read view was built with and the sizes it
+ * saw; see the header comment.  Read-only.  kInvalidArgument: out == NULL. */
+int32_t rrdb_last_view_route(void *h, rrdb_view_route *out);
 
 #ifdef __cplusplus
 }

@@ -218,6 +218,20 @@ class MultiGetLane:
     batch_fallback: int = 0
 
 
+class _ViewRoute(C.Structure):
+    _fields_ = [("rank", C.c_int32), ("bound_levels", C.c_int32), ("n_groups", C.c_uint64),
+                ("window_records", C.c_uint64), ("visible", C.c_uint64)]
+
+
+@dataclass
+class ViewRoute:
+    rank: int = ROUTE_NONE
+    bound_levels: int = 0
+    n_groups: int = 0
+    window_records: int = 0
+    visible: int = 0
+
+
 @dataclass
 class IncrBatchStats:
     input_ops: int = 0
@@ -451,6 +465,10 @@ class RrdbLib:
         if self.has_multi_get_lane:
             L.rrdb_last_multi_get_lane.restype = C.c_int32
             L.rrdb_last_multi_get_lane.argtypes = [C.c_void_p, C.POINTER(_MultiGetLane)]
+        self.has_view_route = hasattr(L, "rrdb_last_view_route")
+        if self.has_view_route:
+            L.rrdb_last_view_route.restype = C.c_int32
+            L.rrdb_last_view_route.argtypes = [C.c_void_p, C.POINTER(_ViewRoute)]
 
     @property
     def backend(self) -> str:
@@ -866,6 +884,22 @@ class RrdbPartition:
         if err != OK:
             raise RuntimeError(f"rrdb_last_multi_get_lane failed: status {err}")
         return MultiGetLane(**{f[0]: getattr(ln, f[0]) for f in _MultiGetLane._fields_})
+
+    # ---- view route: engine-only (include/rrdb_engine_ext.h) ----
+    def last_view_route(self) -> ViewRoute:
+        """Which rank kernel built the last read view on this handle (the
+        ROUTE_RANK_* values, ROUTE_NONE for an empty range), through how many
+        bound-table levels, over how many groups and records, and how many
+        rows the view holds."""
+        if not self.lib.has_view_route:
+            raise RuntimeError(
+                f"last_view_route: backend {self.lib.backend!r} ({self.lib.path}) does not "
+                "export rrdb_last_view_route (engine-only extension)")
+        rt = _ViewRoute()
+        err = self._L.rrdb_last_view_route(self._h, C.byref(rt))
+        if err != OK:
+            raise RuntimeError(f"rrdb_last_view_route failed: status {err}")
+        return ViewRoute(**{f[0]: getattr(rt, f[0]) for f in _ViewRoute._fields_})
 
     # ---- partition split: engine-only (include/rrdb_engine_ext.h) ----
     def split(self, child: "RrdbPartition", new_partition_count: int):

@@ -980,6 +980,10 @@ struct HipEngine {
        branches of multi_get_locked / rrdb_multi_get_batch, read by nothing
        else */
     rrdb_multi_get_lane last_mg_lane{};
+    /* which rank kernel the last read view was built with
+       (rrdb_last_view_route): written at the branches of build_view, read by
+       nothing else */
+    rrdb_view_route last_view{RRDB_ROUTE_NONE, 0, 0, 0, 0};
     int split_crc_lds = 1; /* rrdb_split classify: crc64 table staged in LDS
                               once per workgroup (1, default) or read from
                               global memory (0) (env "engine.split_crc":
@@ -1434,9 +1438,10 @@ struct HipEngine {
         *out_bt = d_bt;
     }
 
-    void build_bound_table(DevRun *dr, int R, const std::vector<uint64_t> &lo,
-                           const std::vector<uint64_t> &hi, const uint64_t *d_lo,
-                           const uint64_t *d_hi, uint64_t **out_bt_off, uint64_t **out_bt)
+    /* returns the number of table levels built (1, or 2 with the coarse one) */
+    int build_bound_table(DevRun *dr, int R, const std::vector<uint64_t> &lo,
+                          const std::vector<uint64_t> &hi, const uint64_t *d_lo,
+                          const uint64_t *d_hi, uint64_t **out_bt_off, uint64_t **out_bt)
     {
         uint64_t wmax = 0;
         for (int r = 0; r < R; r++)
@@ -1448,6 +1453,7 @@ struct HipEngine {
                                     &c_off, &c_bt);
         build_bound_table_level(dr, R, lo, hi, d_lo, d_hi, bt_shift, c_off, c_bt, cshift,
                                 out_bt_off, out_bt);
+        return c_bt ? 2 : 1;
     }
 
     uint64_t *psum_scratch(uint64_t n)
@@ -1525,6 +1531,7 @@ struct HipEngine {
         int R = (int)runs.size();
         *out_view = nullptr;
         *out_n = 0;
+        last_view = rrdb_view_route{RRDB_ROUTE_NONE, 0, 0, 0, 0};
         if (R == 0)
             return;
         DevRun *dr = dev_runs();
@@ -1562,20 +1569,27 @@ struct HipEngine {
         uint8_t *d_shadow = talloc<uint8_t>(total);
         uint64_t *d_flags = talloc<uint64_t>(total * 8);
         uint64_t *d_pos = talloc<uint64_t>(total * 8);
+        last_view.window_records = total;
         if (R > 1 && grp_eligible()) {
             uint64_t *d_anch = nullptr;
             uint64_t n_groups = build_anchors(dr, R, lo, hi, d_lo, d_hi, &d_anch);
+            last_view.rank = RRDB_ROUTE_RANK_GRP;
+            last_view.n_groups = n_groups;
             launch_rank_grp_view(dr, R, d_lo, d_anch, n_groups, d_order, d_shadow, stream);
         } else {
             uint64_t *d_bt_off = nullptr, *d_bt = nullptr;
-            if (R > 1 && total > 100000)
-                build_bound_table(dr, R, lo, hi, d_lo, d_hi, &d_bt_off, &d_bt);
-            if (ldst_eligible())
+            if (R > 1 && total > VIEW_BT_MIN_RECORDS)
+                last_view.bound_levels =
+                    build_bound_table(dr, R, lo, hi, d_lo, d_hi, &d_bt_off, &d_bt);
+            if (ldst_eligible()) {
+                last_view.rank = RRDB_ROUTE_RANK_LDST;
                 launch_rank_ldst(dr, R, d_lo, d_hi, d_wp, total, d_order, d_shadow, d_bt_off,
                                  d_bt, bt_shift, stream);
-            else
+            } else {
+                last_view.rank = RRDB_ROUTE_RANK_GLOBAL;
                 launch_rank(dr, R, d_lo, d_hi, d_wp, total, d_order, d_shadow, d_bt_off, d_bt,
                             bt_shift, stream);
+            }
         }
         launch_visible(dr, d_order, d_shadow, total, d_flags, stream);
         launch_psum(d_flags, d_pos, total, psum_scratch(total), stream);
@@ -1584,6 +1598,7 @@ struct HipEngine {
         HIP_OK(hipMemcpyAsync(&lastf, d_flags + total - 1, 8, hipMemcpyDeviceToHost, stream));
         HIP_OK(hipStreamSynchronize(stream));
         uint64_t nv = lastp + lastf;
+        last_view.visible = nv;
         uint64_t *d_view = nullptr;
         if (nv) {
             HIP_OK(hipMalloc(&d_view, nv * 8));
@@ -3144,6 +3159,16 @@ int32_t rrdb_last_multi_get_lane(void *h, rrdb_multi_get_lane *out)
     auto *e = (HipEngine *)h;
     std::lock_guard<std::mutex> g(e->mu);
     *out = e->last_mg_lane;
+    return RRDB_OK;
+}
+
+int32_t rrdb_last_view_route(void *h, rrdb_view_route *out)
+{
+    if (!out)
+        return RRDB_INVALID_ARGUMENT;
+    auto *e = (HipEngine *)h;
+    std::lock_guard<std::mutex> g(e->mu);
+    *out = e->last_view;
     return RRDB_OK;
 }
 

@@ -29,6 +29,12 @@
  * 2 workgroups/CU).  1024 is the sweet spot. */
 #define GRP_CAP 2048
 #define GRP_TARGET 1024
+/* read view (build_view): the grid cap of the MODE 1 group rank (a workgroup
+ * takes several groups only above it; engine.grp_blocks does not apply to
+ * views), and the window size above which the global and ldst ranks build a
+ * bound table first (at or below it k_rank_ldst searches global memory) */
+#define GRP_VIEW_BLOCKS 3584
+#define VIEW_BT_MIN_RECORDS 100000
 
 /* write batch (rrdb_write_batch): (word, op index) pairs one workgroup sorts
  * in LDS, and the output slice one workgroup merges per pass.  2048 pairs are

@@ -2022,8 +2022,8 @@ void launch_rank_grp_view(const DevRun *d_runs, int R, const uint64_t *d_lo,
     uint64_t blocks = n_groups;
     if (blocks == 0)
         blocks = 1;
-    if (blocks > 3584)
-        blocks = 3584;
+    if (blocks > GRP_VIEW_BLOCKS)
+        blocks = GRP_VIEW_BLOCKS;
     CompactParams cp{};
     ScanParams sp{};
     k_rank_grp<1><<<dim3((uint32_t)blocks), dim3(GRP_BLOCK), 0, s>>>(

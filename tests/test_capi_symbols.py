@@ -63,6 +63,20 @@ def test_multi_get_lane_entry_point_is_engine_only(oracle_part):
         assert hasattr(ctypes.CDLL(HIP_SO), "rrdb_last_multi_get_lane")
 
 
+def test_view_route_entry_point_is_engine_only(oracle_part):
+    """rrdb_last_view_route lives in the extension header: the engine exports
+    it, the oracle does not, and the binding says so."""
+    ext = open(os.path.join(REPO, "include", "rrdb_engine_ext.h")).read()
+    assert re.search(r"\bint32_t\s+rrdb_last_view_route\s*\(\s*void\s*\*h,\s*"
+                     r"rrdb_view_route\s*\*out\s*\)", ext)
+    assert "rrdb_last_view_route" not in open(HEADER).read()
+    assert not oracle_part.lib.has_view_route
+    with pytest.raises(RuntimeError, match="rrdb_last_view_route"):
+        oracle_part.last_view_route()
+    if os.path.exists(HIP_SO):
+        assert hasattr(ctypes.CDLL(HIP_SO), "rrdb_last_view_route")
+
+
 def test_backend_strings():
     lib = ctypes.CDLL(ORACLE_SO)
     lib.rrdb_backend.restype = ctypes.c_char_p

@@ -8,7 +8,11 @@ oracle on every shape, including the branches the main suite cannot reach:
     fallback inside the same segment windows
   - equal-key sets split across a group boundary (anchor key present in
     several runs) -> the s_btail previous-segment shadow check
-  - the scan view build (launch_rank_grp_view) via full drains
+
+The full drains here run after manual_compact: they read one run, which the
+view ranks with the one-run k_rank, so they check the compaction's output and
+not the multi-run view build (launch_rank_grp_view).  That is
+tests/test_read_view_gpu.py.
 
 Reference semantics under test: the compaction-iterator newest-wins /
 tombstone / filter behavior behind do_manual_compact
