@@ -27,155 +27,10 @@
 #include "../../include/rrdb_engine.h"
 #include "../../include/rrdb_engine_ext.h"
 #include "engine_common.h"
+#include "launch.h"
 #include "emit_tile.h"
 #include "wb_stage.h"
 #include "cas_stage.h"
-
-/* ---- launchers (kernels.hip) ---- */
-void launch_crc64_table_init(const uint64_t *host_table);
-void launch_bounds(const DevRun *, int, const uint8_t *, uint64_t, uint64_t *, int, hipStream_t);
-void launch_rank(const DevRun *, int, const uint64_t *, const uint64_t *, const uint64_t *,
-                 uint64_t, uint64_t *, uint8_t *, const uint64_t *, const uint64_t *, int,
-                 hipStream_t);
-void launch_bound_table(const DevRun *, int, const uint64_t *, const uint64_t *,
-                        const uint64_t *, uint64_t, int, uint64_t *, const uint64_t *,
-                        const uint64_t *, int, hipStream_t);
-void launch_visible(const DevRun *, const uint64_t *, const uint8_t *, uint64_t, uint64_t *,
-                    hipStream_t);
-void launch_gather(const uint64_t *, const uint64_t *, const uint64_t *, uint64_t, uint64_t *,
-                   hipStream_t);
-void launch_psum(const uint64_t *, uint64_t *, uint64_t, uint64_t *, hipStream_t);
-uint64_t psum_scratch_elems(uint64_t);
-void launch_get(const DevRun *, int, const uint8_t *, const uint64_t *, uint64_t, uint32_t,
-                uint32_t, int32_t *, uint64_t *, uint64_t *, uint32_t *, hipStream_t);
-void launch_emit_values(const DevRun *, const uint64_t *, const int32_t *, uint64_t, uint32_t,
-                        const uint64_t *, uint8_t *, hipStream_t);
-void launch_scan_state(const DevRun *, const uint64_t *, uint64_t, const ScanParams &, uint8_t *,
-                       uint64_t *, uint64_t *, hipStream_t);
-void launch_normal_flags(const uint8_t *, uint64_t, uint64_t *, hipStream_t);
-void launch_cutoff(const uint64_t *, const uint64_t *, uint64_t, uint64_t, uint64_t *,
-                   hipStream_t);
-void launch_cut_sizes(const uint8_t *, uint64_t, uint64_t, uint64_t *, uint64_t *, hipStream_t);
-void launch_emit_scan(const DevRun *, const uint64_t *, uint64_t, const uint8_t *, uint64_t,
-                      const uint64_t *, const uint64_t *, const uint64_t *, const ScanParams &,
-                      uint8_t *, uint8_t *, uint64_t *, uint64_t *, int32_t *, uint64_t,
-                      hipStream_t);
-void launch_emit_rows(const DevRun *, const uint64_t *, const uint64_t *, uint64_t,
-                      const uint64_t *, const uint64_t *, const ScanParams &, uint8_t *,
-                      uint8_t *, hipStream_t);
-void launch_multi_get_small(const DevRun *, int, const MgFusedArgs &, hipStream_t);
-void launch_multi_get_graph(const DevRun *, int, const uint8_t *, uint8_t *, hipStream_t);
-void launch_mg_server(const DevRun *, int, MgMailbox *, uint8_t *, hipStream_t);
-void launch_bloom_build(const DevRun &, uint64_t *, uint64_t, hipStream_t);
-void launch_bloom_pfx_build(const DevRun &, uint64_t *, uint64_t, hipStream_t);
-void launch_build_tails(const uint8_t *, uint64_t, uint64_t, uint64_t *, hipStream_t);
-void launch_build_meta(const uint8_t *, const uint64_t *, uint64_t, const uint64_t *, uint64_t,
-                       uint32_t, uint64_t *, hipStream_t);
-void launch_rank_compact_lds(const DevRun *, int, const uint64_t *, const uint64_t *,
-                             const uint64_t *, uint64_t, const CompactParams &,
-                             const uint64_t *, const uint64_t *, uint64_t *, uint64_t *,
-                             uint8_t *, uint32_t *, uint64_t *, uint64_t *, CompactStatsDev *,
-                             hipStream_t);
-void launch_valid_beyond(const DevRun *, int, const uint8_t *, uint64_t, int, uint32_t *,
-                         hipStream_t);
-void launch_first_eq(const DevRun *, const uint64_t *, uint64_t, const uint8_t *, uint64_t,
-                     uint32_t *, hipStream_t);
-void launch_rank_ldst(const DevRun *, int, const uint64_t *, const uint64_t *,
-                      const uint64_t *, uint64_t, uint64_t *, uint8_t *, const uint64_t *,
-                      const uint64_t *, int, hipStream_t);
-void launch_anchor_rows(const DevRun *, int, int, const uint64_t *, const uint64_t *, int,
-                        uint64_t, uint64_t *, hipStream_t);
-void launch_rank_grp_compact(const DevRun *, int, const uint64_t *, const uint64_t *, uint64_t,
-                             const CompactParams &, uint64_t *, uint64_t *, uint8_t *,
-                             uint32_t *, uint64_t *, uint64_t *, CompactStatsDev *, int,
-                             hipStream_t);
-void launch_rank_grp_view(const DevRun *, int, const uint64_t *, const uint64_t *, uint64_t,
-                          uint64_t *, uint8_t *, hipStream_t);
-void launch_rank_grp_count(const DevRun *, int, const uint64_t *, const uint64_t *, uint64_t,
-                           const ScanParams &, CompactStatsDev *, hipStream_t);
-void launch_count_single(const DevRun *, const uint64_t *, const uint64_t *,
-                         const ScanParams &, CompactStatsDev *, uint64_t, hipStream_t);
-void launch_rank_compact_ldst(const DevRun *, int, const uint64_t *, const uint64_t *,
-                              const uint64_t *, uint64_t, const CompactParams &, uint64_t *,
-                              uint64_t *, uint8_t *, uint32_t *, uint64_t *, uint64_t *,
-                              uint64_t *, const uint64_t *, const uint64_t *, int,
-                              CompactStatsDev *, hipStream_t);
-void launch_rank_compact(const DevRun *, int, const uint64_t *, const uint64_t *,
-                         const uint64_t *, uint64_t, const CompactParams &, uint64_t *,
-                         uint64_t *, uint8_t *, uint32_t *, uint64_t *, uint64_t *, uint64_t *,
-                         const uint64_t *, const uint64_t *, int, CompactStatsDev *,
-                         hipStream_t);
-void launch_emit_compact_inmajor(const DevRun *, int, const uint64_t *, uint64_t,
-                                 const uint64_t *, const uint64_t *, const uint8_t *,
-                                 const uint32_t *, const uint64_t *, const uint64_t *,
-                                 const uint64_t *, uint32_t, uint8_t *, uint8_t *, uint64_t *,
-                                 uint64_t *, uint64_t *, uint64_t, hipStream_t);
-void launch_emit_compact_chunked(const DevRun *, const uint64_t *, uint64_t, const uint64_t *,
-                                 const uint8_t *, const uint32_t *, const uint64_t *,
-                                 const uint64_t *, const uint64_t *, uint32_t, uint64_t,
-                                 uint64_t, uint64_t, uint64_t *, uint64_t *, uint32_t *,
-                                 uint32_t *, uint8_t *, uint8_t *, uint64_t *, uint64_t *,
-                                 uint64_t *, uint64_t *, uint64_t *, hipStream_t);
-void launch_keep_tile_scan(const uint64_t *, uint64_t, uint32_t *, uint64_t *, uint64_t *,
-                           hipStream_t);
-void launch_emit_fixed_fused(const DevRun *, int, const uint64_t *, uint64_t, const uint64_t *,
-                             const uint64_t *, const uint8_t *, const uint32_t *, uint32_t,
-                             uint32_t, uint32_t, uint64_t, uint8_t *, uint8_t *, uint64_t *,
-                             uint64_t *, uint64_t *, hipStream_t);
-void launch_emit_compact(const DevRun *, const uint64_t *, uint64_t, const uint64_t *,
-                         const uint8_t *, const uint32_t *, const uint64_t *, const uint64_t *,
-                         const uint64_t *, uint32_t, uint8_t *, uint8_t *, uint64_t *, uint64_t *,
-                         uint64_t *, uint64_t, hipStream_t);
-
-void launch_split_classify(const uint8_t *, const uint64_t *, uint64_t, const uint64_t *, uint64_t,
-                           uint64_t, uint64_t, uint64_t, uint8_t *, uint64_t *, uint32_t *, int,
-                           hipStream_t);
-void launch_split_sizes(const uint8_t *, uint32_t, const uint64_t *, const uint64_t *, uint64_t,
-                        uint64_t *, uint64_t *, hipStream_t);
-void launch_split_scatter(const uint8_t *, const uint64_t *, const uint8_t *, const uint64_t *,
-                          const uint64_t *, uint64_t, uint64_t, uint64_t, const uint8_t *,
-                          uint32_t, const uint64_t *, uint64_t, const uint64_t *,
-                          const uint64_t *, uint64_t, uint64_t, uint64_t, uint64_t *, uint64_t *,
-                          uint64_t *, uint64_t *, uint64_t *, hipStream_t);
-void launch_split_copy(const uint64_t *, const uint64_t *, uint64_t, uint64_t, uint64_t,
-                       uint64_t *, uint8_t *, hipStream_t);
-int launch_wb_sort(const WbKeys &, uint64_t, uint32_t *, uint64_t *, uint32_t *, uint64_t *,
-                   uint32_t *, hipStream_t);
-void launch_wb_flags(const WbKeys &, const uint64_t *, uint64_t, const uint8_t *, uint64_t,
-                     const uint64_t *, const uint32_t *, uint64_t *, uint64_t *, uint64_t *,
-                     uint64_t *, hipStream_t);
-void launch_wb_scatter(const WbKeys &, const uint8_t *, const uint64_t *, uint64_t,
-                       const uint8_t *, uint64_t, const uint32_t *, const uint64_t *,
-                       const uint64_t *, const uint64_t *, const uint64_t *, uint64_t, uint64_t,
-                       uint64_t, uint64_t, uint64_t *, uint64_t *, uint64_t *, uint64_t *,
-                       uint64_t *, hipStream_t);
-void launch_incr_heads(const WbKeys &, uint64_t, const uint64_t *, const uint32_t *, uint64_t *,
-                       uint64_t *, hipStream_t);
-void launch_incr_segs(uint64_t, const uint64_t *, const uint64_t *, uint64_t *, uint64_t *,
-                      hipStream_t);
-void launch_incr_chain(const IncrArgs &, hipStream_t);
-void launch_incr_emit(const IncrArgs &, uint64_t, const uint64_t *, const uint64_t *,
-                      const uint64_t *, const uint64_t *, uint64_t, uint64_t, uint64_t, uint64_t,
-                      uint64_t, uint64_t, uint64_t *, uint64_t *, uint64_t *, uint64_t *,
-                      uint8_t *, hipStream_t);
-void launch_cas_heads(const WbKeys &, uint64_t, const uint64_t *, const uint32_t *, uint8_t *,
-                      uint64_t *, uint32_t *, uint64_t *, hipStream_t);
-void launch_cas_group_words(uint64_t, uint64_t, const uint64_t *, const uint32_t *,
-                            const uint64_t *, const uint64_t *, uint8_t *, uint64_t *,
-                            hipStream_t);
-void launch_cas_segs(uint64_t, const uint8_t *, const uint32_t *, uint64_t *, hipStream_t);
-void launch_cas_walk(const CasArgs &, hipStream_t);
-void launch_cas_rows(const CasArgs &, uint64_t *, uint64_t *, uint64_t *, hipStream_t);
-void launch_cas_emit(const CasArgs &, const uint64_t *, const uint64_t *, const uint64_t *,
-                     const uint64_t *, const uint64_t *, uint64_t, uint64_t, uint64_t, uint64_t,
-                     uint64_t *, uint64_t *, uint64_t *, uint64_t *, uint64_t *, hipStream_t);
-void launch_wbt_heads(const WbKeys &, uint64_t, const uint64_t *, const uint32_t *, uint64_t *,
-                      uint64_t *, hipStream_t);
-void launch_wbt_walk(const TtArgs &, hipStream_t);
-void launch_wbt_scatter(const TtArgs &, uint64_t, const uint64_t *, const uint64_t *,
-                        const uint64_t *, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t,
-                        uint64_t, uint64_t *, uint64_t *, uint64_t *, uint64_t *, uint64_t *,
-                        hipStream_t);
 
 #define HIP_OK(x)                                                                                \
     do {                                                                                           \
@@ -4022,6 +3877,19 @@ int32_t rrdb_flush(void *h)
  * buffer proportional to the batch is a plain try allocation owned by WbBufs:
  * the scratch arena aborts when it has to grow, and a full device must come
  * back as kIOError. */
+namespace {
+
+/* the one host-to-device copy of the batch paths: a failed copy clears `ok`
+ * (the call returns kIOError), and nothing is tried once it is clear */
+bool try_upload(bool &ok, void *dst, const void *src, uint64_t bytes)
+{
+    if (ok && bytes && hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipGetLastError();
+        ok = false;
+    }
+    return ok;
+}
+
 struct WbBufs {
     std::vector<void *> dev;
     std::vector<void *> host;
@@ -4049,16 +3917,7 @@ struct WbBufs {
         host.push_back(q);
         return (T *)q;
     }
-    bool upload(void *dst, const void *src, uint64_t bytes)
-    {
-        if (!ok || !bytes)
-            return ok;
-        if (hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipGetLastError();
-            ok = false;
-        }
-        return ok;
-    }
+    bool upload(void *dst, const void *src, uint64_t n) { return try_upload(ok, dst, src, n); }
     ~WbBufs()
     {
         for (void *q : dev)
@@ -4068,10 +3927,11 @@ struct WbBufs {
     }
 };
 
-/* rrdb_incr_batch's sibling of WbBufs: its buffer sizes are all known, or
- * bounded, once n and the key bytes are, so they are pieces of one try
- * allocation (one hipMalloc and one hipFree per call instead of thirty) */
-struct IncrSlab {
+/* WbBufs' sibling for the incr, timetag and cas batches: their buffer sizes
+ * are all known, or bounded, once n and the key bytes are, so they are pieces
+ * of one try allocation (one hipMalloc and one hipFree per call instead of
+ * thirty) */
+struct BatchSlab {
     uint8_t *base = nullptr;
     uint64_t size = 0, used = 0;
     bool ok = true;
@@ -4095,22 +3955,184 @@ struct IncrSlab {
         }
         return ok;
     }
-    bool upload(void *dst, const void *src, uint64_t bytes)
+    bool upload(void *dst, const void *src, uint64_t n) { return try_upload(ok, dst, src, n); }
+    /* an optional per-op column: the caller's array, or zeros when it is null */
+    void upload_or_zero(void *dst, const void *src_or_null, uint64_t bytes)
     {
-        if (!ok || !bytes)
-            return ok;
-        if (hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+        if (src_or_null) {
+            upload(dst, src_or_null, bytes);
+        } else if (ok && hipMemset(dst, 0, bytes) != hipSuccess) {
             (void)hipGetLastError();
             ok = false;
         }
-        return ok;
     }
-    ~IncrSlab()
+    ~BatchSlab()
     {
         if (base)
             (void)hipFree(base);
     }
 };
+
+/* ---- the shared batch-call skeleton: the steps the four batched-write entry
+ * points below have in common, each a call.  What a path does differently
+ * stays written out in its function. ---- */
+
+/* a batch is refused between the begin and the finish of a split compaction
+ * or of a count scan */
+bool batch_blocked(const HipEngine *e) { return e->pend.active || e->pend_scan.active; }
+
+/* after the path's validation.  Pending memtable entries are older than the
+ * batch: their own run first. */
+int32_t batch_begin(HipEngine *e)
+{
+    e->activate();
+    return engine_flush(e);
+}
+
+/* the host-clock keys (<p>_stage, <p>_upload) */
+using HostClock = std::chrono::steady_clock;
+double ms_since(HostClock::time_point t0)
+{
+    return std::chrono::duration<double, std::milli>(HostClock::now() - t0).count();
+}
+
+/* the phase events of one call; destroyed on every way out of it */
+template <int N> struct BatchEvents {
+    hipEvent_t ev[N];
+    BatchEvents()
+    {
+        for (auto &x : ev)
+            HIP_OK(hipEventCreate(&x));
+    }
+    BatchEvents(const BatchEvents &) = delete;
+    BatchEvents &operator=(const BatchEvents &) = delete;
+    ~BatchEvents()
+    {
+        for (auto &x : ev)
+            (void)hipEventDestroy(x);
+    }
+    void record(int i, hipStream_t s) { HIP_OK(hipEventRecord(ev[i], s)); }
+    /* false (and *out untouched) when either event has not completed */
+    bool ms(int i, int j, float *out) const
+    {
+        return hipEventElapsedTime(out, ev[i], ev[j]) == hipSuccess;
+    }
+};
+
+/* <p>_sort, <p>_lookup, <p>_apply, <p>_emit, <p>_total from events 0..5:
+ * 0-1 sort, 1-2 lookup, 2-3 apply, 4-5 emit (0 when nothing was emitted);
+ * the total leaves out the host's wait for the totals between 3 and 4 */
+void batch_phase_timers(HipEngine *e, const char *prefix, const BatchEvents<6> &ev, bool emitted)
+{
+    const std::string p(prefix);
+    float ms = 0;
+    if (ev.ms(0, 1, &ms))
+        e->phase_ms[p + "_sort"] = ms;
+    if (ev.ms(1, 2, &ms))
+        e->phase_ms[p + "_lookup"] = ms;
+    if (ev.ms(2, 3, &ms))
+        e->phase_ms[p + "_apply"] = ms;
+    double &emit = e->phase_ms[p + "_emit"];
+    emit = 0.0;
+    if (emitted && ev.ms(4, 5, &ms))
+        emit = ms;
+    if (ev.ms(0, 3, &ms))
+        e->phase_ms[p + "_total"] = ms + emit;
+}
+
+/* the sorted batch: the words and the op index of every sorted position */
+struct SortedOps {
+    const uint64_t *d_w;
+    const uint32_t *d_ix;
+};
+SortedOps batch_sort(const WbKeys &wk, uint64_t n, uint32_t *d_lcp, uint64_t *d_w0,
+                     uint32_t *d_i0, uint64_t *d_w1, uint32_t *d_i1, hipStream_t s)
+{
+    const int cur = launch_wb_sort(wk, n, d_lcp, d_w0, d_i0, d_w1, d_i1, s);
+    return {cur ? d_w1 : d_w0, cur ? d_i1 : d_i0};
+}
+
+/* one segment per distinct key: head flags, their scan, the segment starts
+ * and the segment count (word 0 of d_red, which this initialises) */
+void batch_segments(const WbKeys &wk, uint64_t n, const SortedOps &so, uint64_t *d_head,
+                    uint64_t *d_hrank, uint64_t *d_seg_start, uint64_t *d_psc, uint64_t *d_red,
+                    int red_words, uint32_t red_min_mask, hipStream_t s)
+{
+    launch_key_heads(wk, n, so.d_w, so.d_ix, d_head, d_red, red_words, red_min_mask, s);
+    launch_psum(d_head, d_hrank, n, d_psc, s);
+    launch_incr_segs(n, d_head, d_hrank, d_seg_start, d_red, s);
+}
+
+/* the bases of a batch: every op's (or check's) key against the runs as they
+ * are now.  The columns exist only when there is something to look up;
+ * status == nullptr is what tells the kernels that there was no lookup. */
+struct BaseLookup {
+    int32_t *status = nullptr;
+    uint64_t *hit = nullptr, *ulen = nullptr;
+    uint32_t *expire = nullptr;
+    DevRun *runs = nullptr;
+    void take(BatchSlab &b, bool lookup, uint64_t n)
+    {
+        if (!lookup)
+            return;
+        b.take(&status, n * 4);
+        b.take(&hit, n * 8);
+        b.take(&ulen, n * 8);
+        b.take(&expire, n * 4);
+    }
+    void get(HipEngine *e, const uint8_t *d_keys, const uint64_t *d_koff, uint64_t n,
+             uint32_t epoch_now)
+    {
+        if (!status)
+            return;
+        runs = e->dev_runs();
+        launch_get(runs, (int)e->runs.size(), d_keys, d_koff, n, epoch_now, e->data_version,
+                   status, hit, ulen, expire, e->stream);
+    }
+};
+
+/* the stride detect_fixed_* would report for a column whose lengths span
+ * [min, max]: the common length, 0 when they differ or it does not fit */
+uint32_t fixed_stride_of(uint64_t min, uint64_t max)
+{
+    return min == max && min <= UINT32_MAX ? (uint32_t)min : 0;
+}
+
+/* the output row of every segment and, for a column that is not fixed-stride,
+ * its byte offset; a fixed-stride column's *d_pos becomes null, which the
+ * emit kernels read as "row x stride" */
+void batch_emit_offsets(uint64_t n_seg, const uint64_t *d_seg_has, uint64_t *d_orank,
+                        const uint64_t *d_seg_ksz, uint64_t **d_kpos, uint32_t out_fk,
+                        const uint64_t *d_seg_vsz, uint64_t **d_vpos, uint32_t out_fv,
+                        uint64_t *d_psc, hipStream_t s)
+{
+    if (out_fk)
+        *d_kpos = nullptr;
+    if (out_fv)
+        *d_vpos = nullptr;
+    launch_psum(d_seg_has, d_orank, n_seg, d_psc, s);
+    if (*d_kpos)
+        launch_psum(d_seg_ksz, *d_kpos, n_seg, d_psc, s);
+    if (*d_vpos)
+        launch_psum(d_seg_vsz, *d_vpos, n_seg, d_psc, s);
+}
+
+/* finish the emitted run and make it the handle's newest; the batch spent
+ * seq_advance seqnos.  false: a try allocation failed, the run is freed.
+ * Either way the stream is drained (finish_run). */
+bool batch_commit_run(HipEngine *e, RunBuf &r, uint64_t seq_advance)
+{
+    if (!e->finish_run(r, nullptr, RunAlloc::Try, e->bloom_enabled)) {
+        e->free_run(r);
+        return false;
+    }
+    e->runs.push_back(r);
+    e->runs_changed();
+    e->next_seq_floor += seq_advance;
+    return true;
+}
+
+} // namespace
 
 extern "C" {
 
@@ -4127,12 +4149,8 @@ int32_t rrdb_write_batch(void *h, uint64_t n_ops, const uint8_t *keys, const uin
     std::lock_guard<std::mutex> g(e->mu);
     if (n_ops == 0)
         return RRDB_OK;
-    using clk = std::chrono::steady_clock;
-    auto ms_since = [](clk::time_point t0) {
-        return std::chrono::duration<double, std::milli>(clk::now() - t0).count();
-    };
-    const auto t_host = clk::now();
-    if (e->pend.active || e->pend_scan.active)
+    const auto t_host = HostClock::now();
+    if (batch_blocked(e))
         return RRDB_INVALID_ARGUMENT;
     if (!wb_validate(n_ops, keys, key_offs, values, val_offs, kinds))
         return RRDB_INVALID_ARGUMENT;
@@ -4141,10 +4159,7 @@ int32_t rrdb_write_batch(void *h, uint64_t n_ops, const uint8_t *keys, const uin
     if (!wb_staged_bytes(n, val_offs, kinds, e->data_version, &sv_bytes))
         return RRDB_INVALID_ARGUMENT;
 
-    /* pending memtable entries are older than the batch: their own run first */
-    e->activate();
-    int32_t rc = engine_flush(e);
-    if (rc != RRDB_OK)
+    if (const int32_t rc = batch_begin(e); rc != RRDB_OK)
         return rc;
 
     /* staging: keys verbatim, values with the header in front of every PUT */
@@ -4159,7 +4174,7 @@ int32_t rrdb_write_batch(void *h, uint64_t n_ops, const uint8_t *keys, const uin
     const uint64_t in_kbytes = key_offs[n];
     e->phase_ms["wb_stage"] = ms_since(t_host);
 
-    const auto t_up = clk::now();
+    const auto t_up = HostClock::now();
     uint8_t *d_keys = b.get<uint8_t>(in_kbytes);
     uint64_t *d_koff = in_fk ? nullptr : b.get<uint64_t>((n + 1) * 8);
     uint8_t *d_svals = b.get<uint8_t>(sv_bytes);
@@ -4186,22 +4201,14 @@ int32_t rrdb_write_batch(void *h, uint64_t n_ops, const uint8_t *keys, const uin
         return RRDB_IO_ERROR;
     e->phase_ms["wb_upload"] = ms_since(t_up);
 
-    hipEvent_t ev[4];
-    for (auto &x : ev)
-        HIP_OK(hipEventCreate(&x));
-    auto drop_events = [&] {
-        for (auto &x : ev)
-            (void)hipEventDestroy(x);
-    };
+    BatchEvents<4> ev;
     const WbKeys wk{d_keys, d_koff, in_fk, d_lcp};
-    HIP_OK(hipEventRecord(ev[0], e->stream));
-    const int cur = launch_wb_sort(wk, n, d_lcp, d_w0, d_i0, d_w1, d_i1, e->stream);
-    const uint64_t *d_w = cur ? d_w1 : d_w0;
-    const uint32_t *d_ix = cur ? d_i1 : d_i0;
-    HIP_OK(hipEventRecord(ev[1], e->stream));
+    ev.record(0, e->stream);
+    const SortedOps so = batch_sort(wk, n, d_lcp, d_w0, d_i0, d_w1, d_i1, e->stream);
+    ev.record(1, e->stream);
 
     /* keep flags, rank, byte offsets; then the one read-back */
-    launch_wb_flags(wk, d_svoff, in_fv, d_kinds, n, d_w, d_ix, d_keep, d_ksz, d_vsz, d_red,
+    launch_wb_flags(wk, d_svoff, in_fv, d_kinds, n, so.d_w, so.d_ix, d_keep, d_ksz, d_vsz, d_red,
                     e->stream);
     launch_psum(d_keep, d_rank, n, d_psc, e->stream);
     uint64_t tot[6] = {0, 0, 0, 0, 0, 0}, red[WBR_WORDS];
@@ -4227,43 +4234,30 @@ int32_t rrdb_write_batch(void *h, uint64_t n_ops, const uint8_t *keys, const uin
     uint64_t *d_row_ksrc = b.get<uint64_t>(n_out * 8), *d_row_vsrc = b.get<uint64_t>(n_out * 8);
     uint64_t *d_kanch = b.get<uint64_t>((((kbytes + 15) >> 10) + 2) * 8);
     uint64_t *d_vanch = b.get<uint64_t>((((vbytes + 15) >> 10) + 2) * 8);
-    if (!b.ok || !e->alloc_base(r, n_out, kbytes, vbytes, RunAlloc::Try)) {
-        drop_events();
+    if (!b.ok || !e->alloc_base(r, n_out, kbytes, vbytes, RunAlloc::Try))
         return RRDB_IO_ERROR;
-    }
     /* the strides detect_fixed_* would report for the emitted run */
-    auto u32_or_0 = [](uint64_t v) { return v > UINT32_MAX ? 0u : (uint32_t)v; };
-    r.fixed_klen = red[WBR_KMIN] == red[WBR_KMAX] ? u32_or_0(red[WBR_KMIN]) : 0;
-    r.fixed_vlen = red[WBR_VMIN] == red[WBR_VMAX] ? u32_or_0(red[WBR_VMIN]) : 0;
-    r.fixed_vlen_put =
-        red[WBR_PUTS] && red[WBR_PVMIN] == red[WBR_PVMAX] ? u32_or_0(red[WBR_PVMIN]) : 0;
-    HIP_OK(hipEventRecord(ev[2], e->stream));
-    launch_wb_scatter(wk, d_svals, d_svoff, in_fv, d_kinds, n, d_ix, d_keep, d_rank, d_kpos,
+    r.fixed_klen = fixed_stride_of(red[WBR_KMIN], red[WBR_KMAX]);
+    r.fixed_vlen = fixed_stride_of(red[WBR_VMIN], red[WBR_VMAX]);
+    r.fixed_vlen_put = red[WBR_PUTS] ? fixed_stride_of(red[WBR_PVMIN], red[WBR_PVMAX]) : 0;
+    ev.record(2, e->stream);
+    launch_wb_scatter(wk, d_svals, d_svoff, in_fv, d_kinds, n, so.d_ix, d_keep, d_rank, d_kpos,
                       d_vpos, e->next_seq_floor, n_out, kbytes, vbytes, r.koff, r.voff, r.sk,
                       d_row_ksrc, d_row_vsrc, e->stream);
     launch_split_copy(d_row_ksrc, r.koff, n_out, r.fixed_klen, kbytes, d_kanch, r.keys,
                       e->stream);
     launch_split_copy(d_row_vsrc, r.voff, n_out, r.fixed_vlen, vbytes, d_vanch, r.vals,
                       e->stream);
-    HIP_OK(hipEventRecord(ev[3], e->stream));
-    if (!e->finish_run(r, nullptr, RunAlloc::Try, e->bloom_enabled)) {
-        e->free_run(r);
-        drop_events();
+    ev.record(3, e->stream);
+    if (!batch_commit_run(e, r, n))
         return RRDB_IO_ERROR;
-    }
     float ms = 0, ms2 = 0;
-    if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
+    if (ev.ms(0, 1, &ms))
         e->phase_ms["wb_sort"] = ms;
-    if (hipEventElapsedTime(&ms, ev[1], ev[2]) == hipSuccess &&
-        hipEventElapsedTime(&ms2, ev[2], ev[3]) == hipSuccess)
+    if (ev.ms(1, 2, &ms) && ev.ms(2, 3, &ms2))
         e->phase_ms["wb_emit"] = ms + ms2;
-    if (hipEventElapsedTime(&ms, ev[0], ev[3]) == hipSuccess)
+    if (ev.ms(0, 3, &ms))
         e->phase_ms["wb_total"] = ms;
-    drop_events();
-
-    e->runs.push_back(r);
-    e->runs_changed();
-    e->next_seq_floor += n;
     if (stats) {
         stats->input_ops = n;
         stats->output_records = n_out;
@@ -4295,34 +4289,31 @@ int32_t rrdb_incr_batch(void *h, uint64_t n_ops, const uint8_t *keys, const uint
     std::lock_guard<std::mutex> g(e->mu);
     if (n_ops == 0)
         return RRDB_OK;
-    if (e->pend.active || e->pend_scan.active)
+    if (batch_blocked(e))
         return RRDB_INVALID_ARGUMENT;
     if (!increments || !wb_keys_ok(n_ops, keys, key_offs))
         return RRDB_INVALID_ARGUMENT;
     const uint64_t n = n_ops;
 
-    /* pending memtable entries are older than the batch: their own run first */
-    e->activate();
-    int32_t rc = engine_flush(e);
-    if (rc != RRDB_OK)
+    if (const int32_t rc = batch_begin(e); rc != RRDB_OK)
         return rc;
 
     /* every buffer proportional to the batch is carved from one try
      * allocation: the sizes are all known from n and the key bytes, the later
      * ones (per segment, per output row) by their upper bound n */
     const uint64_t in_fk = wb_fixed_stride(key_offs, n), in_kbytes = key_offs[n];
-    const int R = (int)e->runs.size();
-    IncrSlab b;
+    BatchSlab b;
+    BaseLookup base;
     uint8_t *d_keys = nullptr;
     uint64_t *d_koff = nullptr, *d_w0 = nullptr, *d_w1 = nullptr, *d_head = nullptr,
-             *d_hrank = nullptr, *d_seg_start = nullptr, *d_psc = nullptr, *d_hit = nullptr,
-             *d_ulen = nullptr, *d_ok = nullptr, *d_okrank = nullptr, *d_seg_has = nullptr,
-             *d_orank = nullptr, *d_seg_ksz = nullptr, *d_seg_vsz = nullptr, *d_red = nullptr,
-             *d_kpos = nullptr, *d_vpos = nullptr, *d_row_ksrc = nullptr, *d_kanch = nullptr;
+             *d_hrank = nullptr, *d_seg_start = nullptr, *d_psc = nullptr, *d_ok = nullptr,
+             *d_okrank = nullptr, *d_seg_has = nullptr, *d_orank = nullptr, *d_seg_ksz = nullptr,
+             *d_seg_vsz = nullptr, *d_red = nullptr, *d_kpos = nullptr, *d_vpos = nullptr,
+             *d_row_ksrc = nullptr, *d_kanch = nullptr;
     int64_t *d_inc = nullptr, *d_newv = nullptr, *d_seg_val = nullptr;
-    int32_t *d_dir = nullptr, *d_status = nullptr, *d_err = nullptr;
-    uint32_t *d_lcp = nullptr, *d_i0 = nullptr, *d_i1 = nullptr, *d_expire = nullptr,
-             *d_seg_exp = nullptr, *d_seg_last = nullptr;
+    int32_t *d_dir = nullptr, *d_err = nullptr;
+    uint32_t *d_lcp = nullptr, *d_i0 = nullptr, *d_i1 = nullptr, *d_seg_exp = nullptr,
+             *d_seg_last = nullptr;
     for (int pass = 0; pass < 2; pass++) { /* 0 sizes the slab, 1 hands the pieces out */
         b.take(&d_keys, in_kbytes);
         b.take(&d_koff, (n + 1) * 8); /* the lookup takes offsets */
@@ -4337,12 +4328,7 @@ int32_t rrdb_incr_batch(void *h, uint64_t n_ops, const uint8_t *keys, const uint
         b.take(&d_hrank, n * 8);
         b.take(&d_seg_start, (n + 1) * 8);
         b.take(&d_psc, psum_scratch_elems(n) * 8);
-        if (R) {
-            b.take(&d_status, n * 4);
-            b.take(&d_hit, n * 8);
-            b.take(&d_ulen, n * 8);
-            b.take(&d_expire, n * 4);
-        }
+        base.take(b, !e->runs.empty(), n);
         b.take(&d_newv, n * 8);
         b.take(&d_err, n * 4);
         b.take(&d_ok, n * 8);
@@ -4365,51 +4351,32 @@ int32_t rrdb_incr_batch(void *h, uint64_t n_ops, const uint8_t *keys, const uint
     b.upload(d_keys, keys, in_kbytes);
     b.upload(d_koff, key_offs, (n + 1) * 8);
     b.upload(d_inc, increments, n * 8);
-    if (expire_ts_seconds) {
-        b.upload(d_dir, expire_ts_seconds, n * 4);
-    } else if (b.ok && hipMemset(d_dir, 0, n * 4) != hipSuccess) {
-        (void)hipGetLastError();
-        b.ok = false;
-    }
+    b.upload_or_zero(d_dir, expire_ts_seconds, n * 4);
     if (!b.ok)
         return RRDB_IO_ERROR;
 
-    hipEvent_t ev[6];
-    for (auto &x : ev)
-        HIP_OK(hipEventCreate(&x));
-    auto drop_events = [&] {
-        for (auto &x : ev)
-            (void)hipEventDestroy(x);
-    };
+    BatchEvents<6> ev;
     /* sort, then the segments: one per distinct key */
     const WbKeys wk{d_keys, in_fk ? nullptr : d_koff, in_fk, d_lcp};
-    HIP_OK(hipEventRecord(ev[0], e->stream));
-    const int cur = launch_wb_sort(wk, n, d_lcp, d_w0, d_i0, d_w1, d_i1, e->stream);
-    const uint64_t *d_w = cur ? d_w1 : d_w0;
-    const uint32_t *d_ix = cur ? d_i1 : d_i0;
-    launch_incr_heads(wk, n, d_w, d_ix, d_head, d_red, e->stream);
-    launch_psum(d_head, d_hrank, n, d_psc, e->stream);
-    launch_incr_segs(n, d_head, d_hrank, d_seg_start, d_red, e->stream);
-    HIP_OK(hipEventRecord(ev[1], e->stream));
-
-    /* the bases: every op's key against the runs as they are now */
-    DevRun *dr = R ? e->dev_runs() : nullptr;
-    if (R)
-        launch_get(dr, R, d_keys, d_koff, n, epoch_now, e->data_version, d_status, d_hit, d_ulen,
-                   d_expire, e->stream);
-    HIP_OK(hipEventRecord(ev[2], e->stream));
+    ev.record(0, e->stream);
+    const SortedOps so = batch_sort(wk, n, d_lcp, d_w0, d_i0, d_w1, d_i1, e->stream);
+    batch_segments(wk, n, so, d_head, d_hrank, d_seg_start, d_psc, d_red, IR_WORDS, IR_MIN_MASK,
+                   e->stream);
+    ev.record(1, e->stream);
+    base.get(e, d_keys, d_koff, n, epoch_now);
+    ev.record(2, e->stream);
 
     IncrArgs a{};
     a.k = wk;
     a.n = n;
-    a.ix = d_ix;
+    a.ix = so.d_ix;
     a.seg_start = d_seg_start;
     a.inc = d_inc;
     a.dir = d_dir;
-    a.status = d_status;
-    a.hit = d_hit;
-    a.expire = d_expire;
-    a.runs = dr;
+    a.status = base.status;
+    a.hit = base.hit;
+    a.expire = base.expire;
+    a.runs = base.runs;
     a.data_version = e->data_version;
     a.epoch_now = epoch_now;
     a.default_ttl = e->default_ttl;
@@ -4426,7 +4393,7 @@ int32_t rrdb_incr_batch(void *h, uint64_t n_ops, const uint8_t *keys, const uint
     a.red = (unsigned long long *)d_red;
     launch_incr_chain(a, e->stream);
     launch_psum(d_ok, d_okrank, n, d_psc, e->stream);
-    HIP_OK(hipEventRecord(ev[3], e->stream));
+    ev.record(3, e->stream);
 
     /* the totals: one read */
     uint64_t red[IR_WORDS];
@@ -4434,9 +4401,8 @@ int32_t rrdb_incr_batch(void *h, uint64_t n_ops, const uint8_t *keys, const uint
     HIP_OK(hipStreamSynchronize(e->stream));
     const uint64_t n_seg = red[IR_NSEG], n_out = red[IR_NOUT];
     const uint64_t kbytes = red[IR_KBYTES], vbytes = red[IR_VBYTES];
-    auto u32_or_0 = [](uint64_t v) { return v > UINT32_MAX ? 0u : (uint32_t)v; };
-    const uint32_t out_fk = n_out && red[IR_KMIN] == red[IR_KMAX] ? u32_or_0(red[IR_KMIN]) : 0;
-    const uint32_t out_fv = n_out && red[IR_VMIN] == red[IR_VMAX] ? u32_or_0(red[IR_VMIN]) : 0;
+    const uint32_t out_fk = n_out ? fixed_stride_of(red[IR_KMIN], red[IR_KMAX]) : 0;
+    const uint32_t out_fv = n_out ? fixed_stride_of(red[IR_VMIN], red[IR_VMAX]) : 0;
 
     auto results_out = [&]() {
         if (new_values)
@@ -4453,64 +4419,31 @@ int32_t rrdb_incr_batch(void *h, uint64_t n_ops, const uint8_t *keys, const uint
             stats->value_bytes = vbytes;
         }
     };
-    auto timers = [&](bool emitted) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
-            e->phase_ms["incr_sort"] = ms;
-        if (hipEventElapsedTime(&ms, ev[1], ev[2]) == hipSuccess)
-            e->phase_ms["incr_lookup"] = ms;
-        if (hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess)
-            e->phase_ms["incr_apply"] = ms;
-        e->phase_ms["incr_emit"] = 0.0;
-        if (emitted && hipEventElapsedTime(&ms, ev[4], ev[5]) == hipSuccess)
-            e->phase_ms["incr_emit"] = ms;
-        float tot = 0;
-        if (hipEventElapsedTime(&tot, ev[0], ev[3]) == hipSuccess)
-            e->phase_ms["incr_total"] = tot + e->phase_ms["incr_emit"];
-    };
     if (n_out == 0) { /* no op wrote: no run, the floor stays */
-        timers(false);
-        drop_events();
+        batch_phase_timers(e, "incr", ev, false);
         results_out();
         return RRDB_OK;
     }
 
     RunBuf r;
-    if (out_fk)
-        d_kpos = nullptr;
-    if (out_fv)
-        d_vpos = nullptr;
     if (n_seg > n || n_out > n_seg || kbytes > in_kbytes ||
-        !e->alloc_base(r, n_out, kbytes, vbytes, RunAlloc::Try)) {
-        drop_events();
+        !e->alloc_base(r, n_out, kbytes, vbytes, RunAlloc::Try))
         return RRDB_IO_ERROR;
-    }
     /* the strides detect_fixed_* would report for the emitted run: all PUTs */
     r.fixed_klen = out_fk;
     r.fixed_vlen = out_fv;
     r.fixed_vlen_put = out_fv;
-    HIP_OK(hipEventRecord(ev[4], e->stream));
-    launch_psum(d_seg_has, d_orank, n_seg, d_psc, e->stream);
-    if (d_kpos)
-        launch_psum(d_seg_ksz, d_kpos, n_seg, d_psc, e->stream);
-    if (d_vpos)
-        launch_psum(d_seg_vsz, d_vpos, n_seg, d_psc, e->stream);
+    ev.record(4, e->stream);
+    batch_emit_offsets(n_seg, d_seg_has, d_orank, d_seg_ksz, &d_kpos, out_fk, d_seg_vsz, &d_vpos,
+                       out_fv, d_psc, e->stream);
     launch_incr_emit(a, n_seg, d_okrank, d_orank, d_kpos, d_vpos, e->next_seq_floor, n_out, kbytes,
                      vbytes, out_fk, out_fv, r.koff, r.voff, r.sk, d_row_ksrc, r.vals, e->stream);
     launch_split_copy(d_row_ksrc, r.koff, n_out, r.fixed_klen, kbytes, d_kanch, r.keys,
                       e->stream);
-    HIP_OK(hipEventRecord(ev[5], e->stream));
-    if (!e->finish_run(r, nullptr, RunAlloc::Try, e->bloom_enabled)) {
-        e->free_run(r);
-        drop_events();
+    ev.record(5, e->stream);
+    if (!batch_commit_run(e, r, red[IR_APPLIED]))
         return RRDB_IO_ERROR;
-    }
-    timers(true);
-    drop_events();
-
-    e->runs.push_back(r);
-    e->runs_changed();
-    e->next_seq_floor += red[IR_APPLIED];
+    batch_phase_timers(e, "incr", ev, true);
     results_out();
     return RRDB_OK;
 }
@@ -4538,12 +4471,8 @@ int32_t rrdb_write_batch_timetag(void *h, uint64_t n_ops, const uint8_t *keys,
     std::lock_guard<std::mutex> g(e->mu);
     if (n_ops == 0)
         return RRDB_OK;
-    using clk = std::chrono::steady_clock;
-    auto ms_since = [](clk::time_point t0) {
-        return std::chrono::duration<double, std::milli>(clk::now() - t0).count();
-    };
-    const auto t_host = clk::now();
-    if (e->pend.active || e->pend_scan.active)
+    const auto t_host = HostClock::now();
+    if (batch_blocked(e))
         return RRDB_INVALID_ARGUMENT;
     if (!wb_validate(n_ops, keys, key_offs, values, val_offs, kinds))
         return RRDB_INVALID_ARGUMENT;
@@ -4552,10 +4481,7 @@ int32_t rrdb_write_batch_timetag(void *h, uint64_t n_ops, const uint8_t *keys,
     if (!wb_staged_bytes(n, val_offs, kinds, e->data_version, &sv_bytes))
         return RRDB_INVALID_ARGUMENT;
 
-    /* pending memtable entries are older than the batch: their own run first */
-    e->activate();
-    int32_t rc = engine_flush(e);
-    if (rc != RRDB_OK)
+    if (const int32_t rc = batch_begin(e); rc != RRDB_OK)
         return rc;
 
     /* staging: keys verbatim, values with header and timetag in front of
@@ -4574,20 +4500,17 @@ int32_t rrdb_write_batch_timetag(void *h, uint64_t n_ops, const uint8_t *keys,
     /* every device buffer proportional to the batch is carved from one try
      * allocation: the later ones (per segment, per output row) by their upper
      * bound n.  Without a verified op no base can matter: no lookup. */
-    const auto t_up = clk::now();
-    const int R = (int)e->runs.size();
-    const bool lookup = R > 0 && verify != nullptr && e->data_version >= 1;
-    IncrSlab b;
+    const auto t_up = HostClock::now();
+    const bool lookup = !e->runs.empty() && verify != nullptr && e->data_version >= 1;
+    BatchSlab b;
+    BaseLookup base;
     uint8_t *d_keys = nullptr, *d_svals = nullptr, *d_flags = nullptr, *d_applied = nullptr;
     uint64_t *d_koff = nullptr, *d_svoff = nullptr, *d_tt = nullptr, *d_w0 = nullptr,
              *d_w1 = nullptr, *d_head = nullptr, *d_hrank = nullptr, *d_seg_start = nullptr,
-             *d_psc = nullptr, *d_hit = nullptr, *d_ulen = nullptr, *d_seg_has = nullptr,
-             *d_orank = nullptr, *d_seg_ksz = nullptr, *d_seg_vsz = nullptr, *d_red = nullptr,
-             *d_kpos = nullptr, *d_vpos = nullptr, *d_row_ksrc = nullptr, *d_row_vsrc = nullptr,
-             *d_kanch = nullptr, *d_vanch = nullptr;
-    int32_t *d_status = nullptr;
-    uint32_t *d_lcp = nullptr, *d_i0 = nullptr, *d_i1 = nullptr, *d_expire = nullptr,
-             *d_seg_last = nullptr;
+             *d_psc = nullptr, *d_seg_has = nullptr, *d_orank = nullptr, *d_seg_ksz = nullptr,
+             *d_seg_vsz = nullptr, *d_red = nullptr, *d_kpos = nullptr, *d_vpos = nullptr,
+             *d_row_ksrc = nullptr, *d_row_vsrc = nullptr, *d_kanch = nullptr, *d_vanch = nullptr;
+    uint32_t *d_lcp = nullptr, *d_i0 = nullptr, *d_i1 = nullptr, *d_seg_last = nullptr;
     for (int pass = 0; pass < 2; pass++) { /* 0 sizes the slab, 1 hands the pieces out */
         b.take(&d_keys, in_kbytes);
         b.take(&d_koff, (n + 1) * 8); /* the lookup takes offsets */
@@ -4604,12 +4527,7 @@ int32_t rrdb_write_batch_timetag(void *h, uint64_t n_ops, const uint8_t *keys,
         b.take(&d_hrank, n * 8);
         b.take(&d_seg_start, (n + 1) * 8);
         b.take(&d_psc, psum_scratch_elems(n) * 8);
-        if (lookup) {
-            b.take(&d_status, n * 4);
-            b.take(&d_hit, n * 8);
-            b.take(&d_ulen, n * 8);
-            b.take(&d_expire, n * 4);
-        }
+        base.take(b, lookup, n);
         b.take(&d_applied, n);
         b.take(&d_seg_last, n * 4);
         b.take(&d_seg_has, n * 8);
@@ -4631,53 +4549,34 @@ int32_t rrdb_write_batch_timetag(void *h, uint64_t n_ops, const uint8_t *keys,
     b.upload(d_svals, h_svals, sv_bytes);
     b.upload(d_svoff, h_svoff, (n + 1) * 8);
     b.upload(d_flags, h_flags, n);
-    if (timetags) {
-        b.upload(d_tt, timetags, n * 8);
-    } else if (b.ok && hipMemset(d_tt, 0, n * 8) != hipSuccess) {
-        (void)hipGetLastError();
-        b.ok = false;
-    }
+    b.upload_or_zero(d_tt, timetags, n * 8);
     if (!b.ok)
         return RRDB_IO_ERROR;
     e->phase_ms["wbt_upload"] = ms_since(t_up);
 
-    hipEvent_t ev[6];
-    for (auto &x : ev)
-        HIP_OK(hipEventCreate(&x));
-    auto drop_events = [&] {
-        for (auto &x : ev)
-            (void)hipEventDestroy(x);
-    };
+    BatchEvents<6> ev;
     /* sort, then the segments: one per distinct key */
     const WbKeys wk{d_keys, in_fk ? nullptr : d_koff, in_fk, d_lcp};
-    HIP_OK(hipEventRecord(ev[0], e->stream));
-    const int cur = launch_wb_sort(wk, n, d_lcp, d_w0, d_i0, d_w1, d_i1, e->stream);
-    const uint64_t *d_w = cur ? d_w1 : d_w0;
-    const uint32_t *d_ix = cur ? d_i1 : d_i0;
-    launch_wbt_heads(wk, n, d_w, d_ix, d_head, d_red, e->stream);
-    launch_psum(d_head, d_hrank, n, d_psc, e->stream);
-    launch_incr_segs(n, d_head, d_hrank, d_seg_start, d_red, e->stream);
-    HIP_OK(hipEventRecord(ev[1], e->stream));
-
-    /* the bases: every op's key against the runs as they are now */
-    DevRun *dr = lookup ? e->dev_runs() : nullptr;
-    if (lookup)
-        launch_get(dr, R, d_keys, d_koff, n, epoch_now, e->data_version, d_status, d_hit, d_ulen,
-                   d_expire, e->stream);
-    HIP_OK(hipEventRecord(ev[2], e->stream));
+    ev.record(0, e->stream);
+    const SortedOps so = batch_sort(wk, n, d_lcp, d_w0, d_i0, d_w1, d_i1, e->stream);
+    batch_segments(wk, n, so, d_head, d_hrank, d_seg_start, d_psc, d_red, TR_WORDS, TR_MIN_MASK,
+                   e->stream);
+    ev.record(1, e->stream);
+    base.get(e, d_keys, d_koff, n, epoch_now);
+    ev.record(2, e->stream);
 
     TtArgs a{};
     a.k = wk;
     a.n = n;
-    a.ix = d_ix;
+    a.ix = so.d_ix;
     a.seg_start = d_seg_start;
     a.flags = d_flags;
     a.tt = d_tt;
     a.svals = d_svals;
     a.svoff = d_svoff;
-    a.status = d_status;
-    a.hit = d_hit;
-    a.runs = dr;
+    a.status = base.status;
+    a.hit = base.hit;
+    a.runs = base.runs;
     a.data_version = e->data_version;
     a.lane_max = e->wbt_lane_max;
     a.applied = d_applied;
@@ -4687,7 +4586,7 @@ int32_t rrdb_write_batch_timetag(void *h, uint64_t n_ops, const uint8_t *keys,
     a.seg_vsz = d_seg_vsz;
     a.red = (unsigned long long *)d_red;
     launch_wbt_walk(a, e->stream);
-    HIP_OK(hipEventRecord(ev[3], e->stream));
+    ev.record(3, e->stream);
 
     /* the totals: one read */
     uint64_t red[TR_WORDS];
@@ -4695,9 +4594,8 @@ int32_t rrdb_write_batch_timetag(void *h, uint64_t n_ops, const uint8_t *keys,
     HIP_OK(hipStreamSynchronize(e->stream));
     const uint64_t n_seg = red[TR_NSEG], n_out = red[TR_NOUT];
     const uint64_t kbytes = red[TR_KBYTES], vbytes = red[TR_VBYTES];
-    auto u32_or_0 = [](uint64_t v) { return v > UINT32_MAX ? 0u : (uint32_t)v; };
-    const uint32_t out_fk = n_out && red[TR_KMIN] == red[TR_KMAX] ? u32_or_0(red[TR_KMIN]) : 0;
-    const uint32_t out_fv = n_out && red[TR_VMIN] == red[TR_VMAX] ? u32_or_0(red[TR_VMIN]) : 0;
+    const uint32_t out_fk = n_out ? fixed_stride_of(red[TR_KMIN], red[TR_KMAX]) : 0;
+    const uint32_t out_fv = n_out ? fixed_stride_of(red[TR_VMIN], red[TR_VMAX]) : 0;
 
     auto results_out = [&]() {
         if (applied)
@@ -4714,72 +4612,36 @@ int32_t rrdb_write_batch_timetag(void *h, uint64_t n_ops, const uint8_t *keys,
             stats->value_bytes = vbytes;
         }
     };
-    auto timers = [&](bool emitted) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
-            e->phase_ms["wbt_sort"] = ms;
-        if (hipEventElapsedTime(&ms, ev[1], ev[2]) == hipSuccess)
-            e->phase_ms["wbt_lookup"] = ms;
-        if (hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess)
-            e->phase_ms["wbt_apply"] = ms;
-        e->phase_ms["wbt_emit"] = 0.0;
-        if (emitted && hipEventElapsedTime(&ms, ev[4], ev[5]) == hipSuccess)
-            e->phase_ms["wbt_emit"] = ms;
-        float tot = 0;
-        if (hipEventElapsedTime(&tot, ev[0], ev[3]) == hipSuccess)
-            e->phase_ms["wbt_total"] = tot + e->phase_ms["wbt_emit"];
-    };
     if (n_seg > n || n_out > n_seg || red[TR_APPLIED] + red[TR_IGNORED] != n ||
-        red[TR_APPLIED] < n_out || kbytes > in_kbytes || vbytes > sv_bytes) {
-        drop_events(); /* cannot happen: the walk's totals contradict the batch */
-        return RRDB_IO_ERROR;
-    }
+        red[TR_APPLIED] < n_out || kbytes > in_kbytes || vbytes > sv_bytes)
+        return RRDB_IO_ERROR; /* cannot happen: the walk's totals contradict the batch */
     if (n_out == 0) { /* every op was ignored: no run; the seqnos are spent all the same */
-        timers(false);
-        drop_events();
+        batch_phase_timers(e, "wbt", ev, false);
         e->next_seq_floor += n;
         results_out();
         return RRDB_OK;
     }
 
     RunBuf r;
-    if (out_fk)
-        d_kpos = nullptr;
-    if (out_fv)
-        d_vpos = nullptr;
-    if (!e->alloc_base(r, n_out, kbytes, vbytes, RunAlloc::Try)) {
-        drop_events();
+    if (!e->alloc_base(r, n_out, kbytes, vbytes, RunAlloc::Try))
         return RRDB_IO_ERROR;
-    }
     /* the strides detect_fixed_* would report for the emitted run */
     r.fixed_klen = out_fk;
     r.fixed_vlen = out_fv;
-    r.fixed_vlen_put =
-        red[TR_PUTS] && red[TR_PVMIN] == red[TR_PVMAX] ? u32_or_0(red[TR_PVMIN]) : 0;
-    HIP_OK(hipEventRecord(ev[4], e->stream));
-    launch_psum(d_seg_has, d_orank, n_seg, d_psc, e->stream);
-    if (d_kpos)
-        launch_psum(d_seg_ksz, d_kpos, n_seg, d_psc, e->stream);
-    if (d_vpos)
-        launch_psum(d_seg_vsz, d_vpos, n_seg, d_psc, e->stream);
+    r.fixed_vlen_put = red[TR_PUTS] ? fixed_stride_of(red[TR_PVMIN], red[TR_PVMAX]) : 0;
+    ev.record(4, e->stream);
+    batch_emit_offsets(n_seg, d_seg_has, d_orank, d_seg_ksz, &d_kpos, out_fk, d_seg_vsz, &d_vpos,
+                       out_fv, d_psc, e->stream);
     launch_wbt_scatter(a, n_seg, d_orank, d_kpos, d_vpos, e->next_seq_floor, n_out, kbytes, vbytes,
                        out_fk, out_fv, r.koff, r.voff, r.sk, d_row_ksrc, d_row_vsrc, e->stream);
     launch_split_copy(d_row_ksrc, r.koff, n_out, r.fixed_klen, kbytes, d_kanch, r.keys,
                       e->stream);
     launch_split_copy(d_row_vsrc, r.voff, n_out, r.fixed_vlen, vbytes, d_vanch, r.vals,
                       e->stream);
-    HIP_OK(hipEventRecord(ev[5], e->stream));
-    if (!e->finish_run(r, nullptr, RunAlloc::Try, e->bloom_enabled)) {
-        e->free_run(r);
-        drop_events();
+    ev.record(5, e->stream);
+    if (!batch_commit_run(e, r, n))
         return RRDB_IO_ERROR;
-    }
-    timers(true);
-    drop_events();
-
-    e->runs.push_back(r);
-    e->runs_changed();
-    e->next_seq_floor += n;
+    batch_phase_timers(e, "wbt", ev, true);
     results_out();
     return RRDB_OK;
 }
@@ -4814,7 +4676,7 @@ int32_t rrdb_check_and_mutate_batch(
     std::lock_guard<std::mutex> g(e->mu);
     if (n_ops == 0)
         return RRDB_OK;
-    if (e->pend.active || e->pend_scan.active)
+    if (batch_blocked(e))
         return RRDB_INVALID_ARGUMENT;
     uint64_t M = 0, sv_bytes = 0;
     if (!cas_validate(n_ops, check_keys, check_key_offs, check_types, operands, operand_offs,
@@ -4823,33 +4685,29 @@ int32_t rrdb_check_and_mutate_batch(
         return RRDB_INVALID_ARGUMENT;
     const uint64_t n = n_ops, E = n + M;
 
-    /* pending memtable entries are older than the batch: their own run first */
-    e->activate();
-    int32_t rc = engine_flush(e);
-    if (rc != RRDB_OK)
+    if (const int32_t rc = batch_begin(e); rc != RRDB_OK)
         return rc;
 
     /* one try allocation for everything proportional to n + M; the columns
      * the host stages come first, so that they go up in one copy */
     const uint64_t ck_bytes = check_key_offs[n], mk_bytes = mut_key_offs[M];
     const uint64_t ek_bytes = ck_bytes + mk_bytes, op_bytes = operand_offs[n];
-    const int R = (int)e->runs.size();
-    IncrSlab b;
+    BatchSlab b;
+    BaseLookup base;
     uint8_t *d_ekeys = nullptr, *d_evals = nullptr, *d_ekind = nullptr, *d_opfl = nullptr,
             *d_ckeys = nullptr, *d_opd = nullptr, *d_khead = nullptr, *d_words = nullptr,
             *d_exist = nullptr;
     uint64_t *d_ekoff = nullptr, *d_evoff = nullptr, *d_ckoff = nullptr, *d_opoff = nullptr,
              *d_moff = nullptr, *d_w0 = nullptr, *d_w1 = nullptr, *d_hhead = nullptr,
              *d_hrank = nullptr, *d_gw0 = nullptr, *d_gw1 = nullptr, *d_seg_start = nullptr,
-             *d_psc = nullptr, *d_hit = nullptr, *d_ulen = nullptr, *d_applied = nullptr,
-             *d_arank = nullptr, *d_cv_src = nullptr, *d_cv_len = nullptr, *d_cv_off = nullptr,
-             *d_row = nullptr, *d_orank = nullptr, *d_ksz = nullptr, *d_vsz = nullptr,
-             *d_kpos = nullptr, *d_vpos = nullptr, *d_row_ksrc = nullptr, *d_row_vsrc = nullptr,
-             *d_kanch = nullptr, *d_vanch = nullptr, *d_red = nullptr;
+             *d_psc = nullptr, *d_applied = nullptr, *d_arank = nullptr, *d_cv_src = nullptr,
+             *d_cv_len = nullptr, *d_cv_off = nullptr, *d_row = nullptr, *d_orank = nullptr,
+             *d_ksz = nullptr, *d_vsz = nullptr, *d_kpos = nullptr, *d_vpos = nullptr,
+             *d_row_ksrc = nullptr, *d_row_vsrc = nullptr, *d_kanch = nullptr, *d_vanch = nullptr,
+             *d_red = nullptr;
     uint32_t *d_lcp = nullptr, *d_i0 = nullptr, *d_i1 = nullptr, *d_pos = nullptr,
-             *d_glcp = nullptr, *d_gi0 = nullptr, *d_gi1 = nullptr, *d_expire = nullptr,
-             *d_eff = nullptr;
-    int32_t *d_ct = nullptr, *d_status = nullptr, *d_err = nullptr;
+             *d_glcp = nullptr, *d_gi0 = nullptr, *d_gi1 = nullptr, *d_eff = nullptr;
+    int32_t *d_ct = nullptr, *d_err = nullptr;
     uint64_t up_bytes = 0;
     for (int pass = 0; pass < 2; pass++) { /* 0 sizes the slab, 1 hands the pieces out */
         b.take(&d_ekeys, ek_bytes);
@@ -4882,12 +4740,7 @@ int32_t rrdb_check_and_mutate_batch(
         b.take(&d_gi1, n * 4);
         b.take(&d_seg_start, (n + 1) * 8);
         b.take(&d_psc, psum_scratch_elems(E) * 8);
-        if (R) {
-            b.take(&d_status, n * 4);
-            b.take(&d_hit, n * 8);
-            b.take(&d_ulen, n * 8);
-            b.take(&d_expire, n * 4);
-        }
+        base.take(b, !e->runs.empty(), n);
         b.take(&d_eff, E * 4);
         b.take(&d_applied, E * 8);
         b.take(&d_arank, E * 8);
@@ -4937,40 +4790,27 @@ int32_t rrdb_check_and_mutate_batch(
     if (!b.ok)
         return RRDB_IO_ERROR;
 
-    hipEvent_t ev[6];
-    for (auto &x : ev)
-        HIP_OK(hipEventCreate(&x));
-    auto drop_events = [&] {
-        for (auto &x : ev)
-            (void)hipEventDestroy(x);
-    };
+    BatchEvents<6> ev;
     /* sort the entries; key heads, hashkey groups, the ops by group */
     const WbKeys wk{d_ekeys, in_fk ? nullptr : d_ekoff, in_fk, d_lcp};
-    HIP_OK(hipEventRecord(ev[0], e->stream));
-    const int cur = launch_wb_sort(wk, E, d_lcp, d_w0, d_i0, d_w1, d_i1, e->stream);
-    const uint64_t *d_w = cur ? d_w1 : d_w0;
-    const uint32_t *d_ix = cur ? d_i1 : d_i0;
-    launch_cas_heads(wk, E, d_w, d_ix, d_khead, d_hhead, d_pos, d_red, e->stream);
+    ev.record(0, e->stream);
+    const SortedOps so = batch_sort(wk, E, d_lcp, d_w0, d_i0, d_w1, d_i1, e->stream);
+    launch_cas_heads(wk, E, so.d_w, so.d_ix, d_khead, d_hhead, d_pos, d_red, e->stream);
     launch_psum(d_hhead, d_hrank, E, d_psc, e->stream);
     launch_cas_group_words(n, E, d_moff, d_pos, d_hhead, d_hrank, d_words, d_red, e->stream);
     const WbKeys gk{d_words, nullptr, 8, d_glcp};
-    const int gcur = launch_wb_sort(gk, n, d_glcp, d_gw0, d_gi0, d_gw1, d_gi1, e->stream);
-    const uint32_t *d_ops = gcur ? d_gi1 : d_gi0;
+    const uint32_t *d_ops =
+        batch_sort(gk, n, d_glcp, d_gw0, d_gi0, d_gw1, d_gi1, e->stream).d_ix;
     launch_cas_segs(n, d_words, d_ops, d_seg_start, e->stream);
-    HIP_OK(hipEventRecord(ev[1], e->stream));
-
-    /* the bases: every check key against the runs as they are now */
-    DevRun *dr = R ? e->dev_runs() : nullptr;
-    if (R)
-        launch_get(dr, R, d_ckeys, d_ckoff, n, epoch_now, e->data_version, d_status, d_hit,
-                   d_ulen, d_expire, e->stream);
-    HIP_OK(hipEventRecord(ev[2], e->stream));
+    ev.record(1, e->stream);
+    base.get(e, d_ckeys, d_ckoff, n, epoch_now); /* the check keys' */
+    ev.record(2, e->stream);
 
     CasArgs a{};
     a.k = wk;
     a.n = n;
     a.E = E;
-    a.ix = d_ix;
+    a.ix = so.d_ix;
     a.pos = d_pos;
     a.khead = d_khead;
     a.svals = d_evals;
@@ -4983,9 +4823,9 @@ int32_t rrdb_check_and_mutate_batch(
     a.moff = d_moff;
     a.ops = d_ops;
     a.seg_start = d_seg_start;
-    a.status = d_status;
-    a.hit = d_hit;
-    a.runs = dr;
+    a.status = base.status;
+    a.hit = base.hit;
+    a.runs = base.runs;
     a.data_version = e->data_version;
     a.epoch_now = epoch_now;
     a.eff = d_eff;
@@ -5003,7 +4843,7 @@ int32_t rrdb_check_and_mutate_batch(
     launch_psum(d_vsz, d_vpos, E, d_psc, e->stream);
     if (check_values)
         launch_psum(d_cv_len, d_cv_off, n, d_psc, e->stream);
-    HIP_OK(hipEventRecord(ev[3], e->stream));
+    ev.record(3, e->stream);
 
     /* the totals: one read */
     uint64_t red[CR_WORDS];
@@ -5012,14 +4852,12 @@ int32_t rrdb_check_and_mutate_batch(
     const uint64_t n_out = red[CR_NOUT], kbytes = red[CR_KBYTES], vbytes = red[CR_VBYTES];
     const uint64_t applied = red[CR_APPLIED], ret_bytes = red[CR_RETBYTES];
     if (n_out > M || applied > M || kbytes > mk_bytes || vbytes > sv_bytes ||
-        (n_out == 0) != (applied == 0)) {
-        drop_events();
+        (n_out == 0) != (applied == 0))
         return RRDB_IO_ERROR; /* cannot happen: the totals come from the staged columns */
-    }
 
     /* the returned check values: gathered into one device buffer, then one
      * copy into the result's arena */
-    HIP_OK(hipEventRecord(ev[4], e->stream));
+    ev.record(4, e->stream);
     WbBufs cvb;
     if (check_values) {
         Arena *ar = result_init(check_values);
@@ -5028,10 +4866,8 @@ int32_t rrdb_check_and_mutate_batch(
         uint64_t *h_len = cvb.get_host<uint64_t>(n * 8);
         const uint64_t anch_bytes = ((((ret_bytes + 15) >> 10) + 2) * 8 + 255) & ~255ull;
         uint8_t *d_cv = ret_bytes ? cvb.get<uint8_t>(anch_bytes + ret_bytes) : nullptr;
-        if (!sl || !blk || !cvb.ok) {
-            drop_events();
+        if (!sl || !blk || !cvb.ok)
             return RRDB_IO_ERROR;
-        }
         if (ret_bytes) {
             HIP_OK(hipMemcpyAsync(d_cv_off + n, d_red + CR_RETBYTES, 8, hipMemcpyDeviceToDevice,
                                   e->stream));
@@ -5047,10 +4883,8 @@ int32_t rrdb_check_and_mutate_batch(
             sl[i] = {blk + at, h_len[i]};
             at += h_len[i];
         }
-        if (at != ret_bytes) {
-            drop_events();
+        if (at != ret_bytes)
             return RRDB_IO_ERROR; /* cannot happen: one column, summed twice */
-        }
         check_values->values = sl;
         check_values->count = n;
         check_values->error = RRDB_OK;
@@ -5075,59 +4909,34 @@ int32_t rrdb_check_and_mutate_batch(
             stats->value_bytes = vbytes;
         }
     };
-    auto timers = [&]() {
-        float ms = 0, tot = 0;
-        if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
-            e->phase_ms["cas_sort"] = ms;
-        if (hipEventElapsedTime(&ms, ev[1], ev[2]) == hipSuccess)
-            e->phase_ms["cas_lookup"] = ms;
-        if (hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess)
-            e->phase_ms["cas_apply"] = ms;
-        e->phase_ms["cas_emit"] = 0.0;
-        if (hipEventElapsedTime(&ms, ev[4], ev[5]) == hipSuccess)
-            e->phase_ms["cas_emit"] = ms;
-        if (hipEventElapsedTime(&tot, ev[0], ev[3]) == hipSuccess)
-            e->phase_ms["cas_total"] = tot + e->phase_ms["cas_emit"];
-    };
+    /* cas_emit runs from event 4, so it covers the check-value gather above,
+     * and is measured on the no-run path too */
     if (n_out == 0) { /* no check passed: no run, the floor stays */
-        HIP_OK(hipEventRecord(ev[5], e->stream));
+        ev.record(5, e->stream);
         HIP_OK(hipStreamSynchronize(e->stream));
-        timers();
-        drop_events();
+        batch_phase_timers(e, "cas", ev, true);
         results_out();
         return RRDB_OK;
     }
 
     RunBuf r;
-    if (!e->alloc_base(r, n_out, kbytes, vbytes, RunAlloc::Try)) {
-        drop_events();
+    if (!e->alloc_base(r, n_out, kbytes, vbytes, RunAlloc::Try))
         return RRDB_IO_ERROR;
-    }
     /* the strides detect_fixed_* would report for the emitted run */
-    auto u32_or_0 = [](uint64_t v) { return v > UINT32_MAX ? 0u : (uint32_t)v; };
-    r.fixed_klen = red[CR_KMIN] == red[CR_KMAX] ? u32_or_0(red[CR_KMIN]) : 0;
-    r.fixed_vlen = red[CR_VMIN] == red[CR_VMAX] ? u32_or_0(red[CR_VMIN]) : 0;
-    r.fixed_vlen_put =
-        red[CR_PUTS] && red[CR_PVMIN] == red[CR_PVMAX] ? u32_or_0(red[CR_PVMIN]) : 0;
+    r.fixed_klen = fixed_stride_of(red[CR_KMIN], red[CR_KMAX]);
+    r.fixed_vlen = fixed_stride_of(red[CR_VMIN], red[CR_VMAX]);
+    r.fixed_vlen_put = red[CR_PUTS] ? fixed_stride_of(red[CR_PVMIN], red[CR_PVMAX]) : 0;
     launch_cas_emit(a, d_row, d_orank, d_kpos, d_vpos, d_arank, e->next_seq_floor, n_out, kbytes,
                     vbytes, r.koff, r.voff, r.sk, d_row_ksrc, d_row_vsrc, e->stream);
     launch_split_copy(d_row_ksrc, r.koff, n_out, r.fixed_klen, kbytes, d_kanch, r.keys,
                       e->stream);
     launch_split_copy(d_row_vsrc, r.voff, n_out, r.fixed_vlen, vbytes, d_vanch, r.vals,
                       e->stream);
-    HIP_OK(hipEventRecord(ev[5], e->stream));
-    if (!e->finish_run(r, nullptr, RunAlloc::Try, e->bloom_enabled)) {
-        e->free_run(r);
-        drop_events();
+    ev.record(5, e->stream);
+    if (!batch_commit_run(e, r, applied))
         return RRDB_IO_ERROR;
-    }
     HIP_OK(hipStreamSynchronize(e->stream));
-    timers();
-    drop_events();
-
-    e->runs.push_back(r);
-    e->runs_changed();
-    e->next_seq_floor += applied;
+    batch_phase_timers(e, "cas", ev, true);
     results_out();
     return RRDB_OK;
 }
@@ -5322,12 +5131,6 @@ int32_t rrdb_restore(void *h, const char *dir, uint64_t decree)
  * reference's concurrent THREAD_POOL_SCAN handlers in a single launch.
  * Requests whose ranges exceed the fused budget (or exotic shared params)
  * fall back to the general per-request path. */
-void launch_multi_get_batch(const DevRun *, int, const MgFusedArgs &, const uint8_t *,
-                            const uint64_t *, uint64_t, int64_t *, uint8_t *, uint64_t,
-                            hipStream_t);
-void launch_pack_blobs(const uint8_t *, uint64_t, uint64_t, const uint64_t *, const uint64_t *,
-                       uint8_t *, hipStream_t);
-
 extern "C" int32_t rrdb_multi_get_batch(void *h, uint64_t n_req, const uint8_t *hash_keys,
                                         const uint64_t *hk_offs,
                                         const rrdb_multi_get_request *shared,

@@ -50,10 +50,15 @@ struct WbKeys {
     const uint32_t *lcp;  /* device: L, the prefix all keys share */
 };
 
-/* write-batch emit reduction (one block of u64 words, vector atomics) */
+/* write-batch emit reduction (one block of u64 words, vector atomics).  Of
+ * every batch path's block the words in *_MIN_MASK fold with min and start at
+ * ~0, those in *_MAX_MASK with max, the rest are sums (kernels.hip red_init,
+ * red_fold). */
 enum {
     WBR_KMIN = 0, WBR_KMAX, WBR_VMIN, WBR_VMAX, WBR_PVMIN, WBR_PVMAX, WBR_PUTS, WBR_WORDS
 };
+#define WBR_MIN_MASK (1u << WBR_KMIN | 1u << WBR_VMIN | 1u << WBR_PVMIN)
+#define WBR_MAX_MASK (1u << WBR_KMAX | 1u << WBR_VMAX | 1u << WBR_PVMAX)
 
 struct DevRun;
 
@@ -68,6 +73,8 @@ enum {
     IR_NSEG = 0, IR_APPLIED, IR_FPARSE, IR_FRANGE, IR_NOUT, IR_KBYTES, IR_VBYTES,
     IR_KMIN, IR_KMAX, IR_VMIN, IR_VMAX, IR_WORDS
 };
+#define IR_MIN_MASK (1u << IR_KMIN | 1u << IR_VMIN)
+#define IR_MAX_MASK (1u << IR_KMAX | 1u << IR_VMAX)
 
 #define INCR_NO_OP 0xFFFFFFFFu
 /* errors[i] of a failed op: RRDB_INVALID_ARGUMENT (engine.cpp asserts the two agree) */
@@ -112,6 +119,9 @@ enum {
     TR_NSEG = 0, TR_APPLIED, TR_IGNORED, TR_NOUT, TR_PUTS, TR_KBYTES, TR_VBYTES,
     TR_KMIN, TR_KMAX, TR_VMIN, TR_VMAX, TR_PVMIN, TR_PVMAX, TR_WORDS
 };
+static_assert(TR_NSEG == IR_NSEG, "k_incr_segs writes the segment count of both paths");
+#define TR_MIN_MASK (1u << TR_KMIN | 1u << TR_VMIN | 1u << TR_PVMIN)
+#define TR_MAX_MASK (1u << TR_KMAX | 1u << TR_VMAX | 1u << TR_PVMAX)
 
 #define WBT_NO_OP 0xFFFFFFFFu
 
@@ -147,6 +157,8 @@ enum {
     CR_NOUT, CR_PUTS, CR_KBYTES, CR_VBYTES, CR_KMIN, CR_KMAX, CR_VMIN, CR_VMAX, CR_PVMIN,
     CR_PVMAX, CR_WORDS
 };
+#define CR_MIN_MASK (1u << CR_KMIN | 1u << CR_VMIN | 1u << CR_PVMIN)
+#define CR_MAX_MASK (1u << CR_KMAX | 1u << CR_VMAX | 1u << CR_PVMAX)
 
 #define CAS_NONE 0xFFFFFFFFu
 /* errors[i]: RRDB_INVALID_ARGUMENT / RRDB_TRY_AGAIN (engine.cpp asserts they agree) */

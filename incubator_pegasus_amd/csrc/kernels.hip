@@ -40,6 +40,7 @@
 #include "emit_tile.h"
 #include "grp_stage.h"
 #include "engine_common.h"
+#include "launch.h"
 
 #define WAVE 64
 #define BLOCK 256
@@ -2051,8 +2052,6 @@ void launch_count_single(const DevRun *d_runs, const uint64_t *d_lo, const uint6
     k_count_single<<<grid_for(n_max, BLOCK), BLOCK, 0, s>>>(d_runs, d_lo, d_hi, sp, d_stats);
 }
 
-/* fused count scan: shadow + countability evaluated in-kernel, the count
- * lands in stats->output_records (banked); zero intermediate arrays */
 void launch_rank_grp_count(const DevRun *d_runs, int R, const uint64_t *d_lo,
                            const uint64_t *d_anch, uint64_t n_groups, const ScanParams &sp,
                            CompactStatsDev *d_stats, hipStream_t s)
@@ -2698,8 +2697,6 @@ void launch_gather(const uint64_t *d_order, const uint64_t *d_flags, const uint6
     k_gather<<<grid_for(m, BLOCK), BLOCK, 0, s>>>(d_order, d_flags, d_pos, m, d_out);
 }
 
-/* exclusive scan; caller provides scratch of psum_scratch_elems(n) u64s
- * (engine-owned arena — no per-call allocation) */
 uint64_t psum_scratch_elems(uint64_t n)
 {
     uint64_t tot = 0;
@@ -2844,8 +2841,6 @@ void launch_emit_compact_chunked(const DevRun *d_runs, const uint64_t *d_order, 
                                                                 dv, d_vout);
 }
 
-/* all-fixed-stride route, first half (compact_begin): per-tile keep counts
- * and their exclusive scan; *d_total receives the output row count */
 void launch_keep_tile_scan(const uint64_t *d_keepw, uint64_t m, uint32_t *d_tile_cnt,
                            uint64_t *d_tile_base, uint64_t *d_total, hipStream_t s)
 {
@@ -2855,8 +2850,6 @@ void launch_keep_tile_scan(const uint64_t *d_keepw, uint64_t m, uint32_t *d_tile
     k_keep_tile_scan<<<1, BLOCK, 0, s>>>(d_tile_cnt, n_tiles, d_tile_base, d_total);
 }
 
-/* second half (compact_finish, n_out > 0): the fused scan + row build + copy.
- * d_changed / d_new_expire are null when the pass can rewrite nothing */
 void launch_emit_fixed_fused(const DevRun *d_runs, int R, const uint64_t *d_order, uint64_t m,
                              const uint64_t *d_keepw, const uint64_t *d_tile_base,
                              const uint8_t *d_changed, const uint32_t *d_new_expire, uint32_t dv,
@@ -3970,10 +3963,6 @@ void launch_split_scatter(const uint8_t *keys, const uint64_t *koff, const uint8
         n_side, kbytes, vbytes, d_okoff, d_ovoff, d_osk, d_row_ksrc, d_row_vsrc);
 }
 
-/* move one column's bytes (keys or values) of a split side: rows gathered
- * from d_row_src into the packed d_out.  stride != 0: every row has that
- * length; else d_row_off[n_rows+1] holds the 0-based output offsets and
- * d_anchor (((bytes+15)>>10)+1 words) is scratch for the chunk->row search */
 void launch_split_copy(const uint64_t *d_row_src, const uint64_t *d_row_off, uint64_t n_rows,
                        uint64_t stride, uint64_t bytes, uint64_t *d_anchor, uint8_t *d_out,
                        hipStream_t s)
@@ -4234,6 +4223,43 @@ __global__ void __launch_bounds__(BLOCK)
     }
 }
 
+/* ---- the reduction block of a batch path (engine_common.h: WBR_*, IR_*,
+ * TR_*, CR_*): min words start at ~0, the rest at 0; every workgroup tallies
+ * into an LDS copy and folds that into the device block once ---- */
+static void red_init(uint64_t *d_red, int words, uint32_t min_mask, hipStream_t s)
+{
+    uint64_t init[32];
+    for (int j = 0; j < words; j++)
+        init[j] = (min_mask >> j & 1) ? ~0ull : 0ull;
+    HIP_CHECK(hipMemcpyAsync(d_red, init, words * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+}
+
+__device__ static inline void red_lds_init(unsigned long long *s_red, uint32_t words,
+                                           uint32_t min_mask)
+{
+    if (threadIdx.x < words)
+        s_red[threadIdx.x] = (min_mask >> threadIdx.x & 1) ? ~0ull : 0ull;
+    __syncthreads();
+}
+
+/* words [first_word, first_word + n_words) of the LDS copy into the device
+ * block; a sum that is zero is skipped */
+__device__ static inline void red_fold(const unsigned long long *s_red, unsigned long long *red,
+                                       uint32_t first_word, uint32_t n_words,
+                                       uint32_t min_mask, uint32_t max_mask)
+{
+    __syncthreads();
+    if (threadIdx.x >= first_word && threadIdx.x < first_word + n_words) {
+        const unsigned long long v = s_red[threadIdx.x];
+        if (min_mask >> threadIdx.x & 1)
+            atomicMin(&red[threadIdx.x], v);
+        else if (max_mask >> threadIdx.x & 1)
+            atomicMax(&red[threadIdx.x], v);
+        else if (v)
+            atomicAdd(&red[threadIdx.x], v);
+    }
+}
+
 /* keep[p] = 1 iff sorted position p holds the newest op of its key; its key
  * and encoded-value sizes (0 when dropped) for the byte-offset scans (a null
  * output = that column is fixed-stride); and the kept rows' length min/max,
@@ -4244,12 +4270,7 @@ __global__ void __launch_bounds__(BLOCK)
                uint64_t *vsz, unsigned long long *red)
 {
     __shared__ unsigned long long s_red[WBR_WORDS];
-    if (threadIdx.x < WBR_WORDS)
-        s_red[threadIdx.x] = (threadIdx.x == WBR_KMIN || threadIdx.x == WBR_VMIN ||
-                              threadIdx.x == WBR_PVMIN)
-                                 ? ~0ull
-                                 : 0ull;
-    __syncthreads();
+    red_lds_init(s_red, WBR_WORDS, WBR_MIN_MASK);
     const uint64_t L = *k.lcp;
     unsigned long long kmin = ~0ull, kmax = 0, vmin = ~0ull, vmax = 0, pvmin = ~0ull, pvmax = 0,
                        puts = 0;
@@ -4288,16 +4309,7 @@ __global__ void __launch_bounds__(BLOCK)
             atomicAdd(&s_red[WBR_PUTS], puts);
         }
     }
-    __syncthreads();
-    if (threadIdx.x < WBR_WORDS) {
-        const unsigned long long v = s_red[threadIdx.x];
-        if (threadIdx.x == WBR_KMIN || threadIdx.x == WBR_VMIN || threadIdx.x == WBR_PVMIN)
-            atomicMin(&red[threadIdx.x], v);
-        else if (threadIdx.x == WBR_PUTS)
-            atomicAdd(&red[threadIdx.x], v);
-        else
-            atomicMax(&red[threadIdx.x], v);
-    }
+    red_fold(s_red, red, 0, WBR_WORDS, WBR_MIN_MASK, WBR_MAX_MASK);
 }
 
 /* the kept ops, by rank: osk, 0-based okoff/ovoff (n_out+1 entries) and the
@@ -4337,8 +4349,6 @@ static inline uint32_t wb_tile_grid(uint64_t n)
     return (uint32_t)(t > (1u << 20) ? (1u << 20) : (t ? t : 1));
 }
 
-/* sort the batch's (word, index) pairs; d_lcp is 4 bytes of scratch that
- * k.lcp points at.  Returns 0 / 1: the result is in (w0, i0) / (w1, i1). */
 int launch_wb_sort(const WbKeys &k, uint64_t n, uint32_t *d_lcp, uint64_t *d_w0, uint32_t *d_i0,
                    uint64_t *d_w1, uint32_t *d_i1, hipStream_t s)
 {
@@ -4356,16 +4366,12 @@ int launch_wb_sort(const WbKeys &k, uint64_t n, uint32_t *d_lcp, uint64_t *d_w0,
     return cur;
 }
 
-/* d_red: WBR_WORDS u64 words, initialised here */
 void launch_wb_flags(const WbKeys &k, const uint64_t *d_svoff, uint64_t fv,
                      const uint8_t *d_kinds, uint64_t n, const uint64_t *d_w,
                      const uint32_t *d_ix, uint64_t *d_keep, uint64_t *d_ksz, uint64_t *d_vsz,
                      uint64_t *d_red, hipStream_t s)
 {
-    uint64_t init[WBR_WORDS];
-    for (int j = 0; j < WBR_WORDS; j++)
-        init[j] = (j == WBR_KMIN || j == WBR_VMIN || j == WBR_PVMIN) ? ~0ull : 0ull;
-    HIP_CHECK(hipMemcpyAsync(d_red, init, sizeof(init), hipMemcpyHostToDevice, s));
+    red_init(d_red, WBR_WORDS, WBR_MIN_MASK, s);
     k_wb_flags<<<grid_for(n, BLOCK), BLOCK, 0, s>>>(k, d_svoff, fv, d_kinds, n, d_w, d_ix, d_keep,
                                                    d_ksz, d_vsz, (unsigned long long *)d_red);
 }
@@ -4551,9 +4557,7 @@ __device__ static void incr_walk(const IncrArgs &a, uint64_t s, uint64_t beg, ui
 __device__ static inline void incr_tally_flush(const IncrTally &t, unsigned long long *s_red,
                                                unsigned long long *red)
 {
-    if (threadIdx.x < IR_WORDS)
-        s_red[threadIdx.x] = (threadIdx.x == IR_KMIN || threadIdx.x == IR_VMIN) ? ~0ull : 0ull;
-    __syncthreads();
+    red_lds_init(s_red, IR_WORDS, IR_MIN_MASK);
     if (t.applied)
         atomicAdd(&s_red[IR_APPLIED], t.applied);
     if (t.fparse)
@@ -4569,16 +4573,7 @@ __device__ static inline void incr_tally_flush(const IncrTally &t, unsigned long
         atomicMin(&s_red[IR_VMIN], t.vmin);
         atomicMax(&s_red[IR_VMAX], t.vmax);
     }
-    __syncthreads();
-    if (threadIdx.x > IR_NSEG && threadIdx.x < IR_WORDS) {
-        const unsigned long long v = s_red[threadIdx.x];
-        if (threadIdx.x == IR_KMIN || threadIdx.x == IR_VMIN)
-            atomicMin(&red[threadIdx.x], v);
-        else if (threadIdx.x == IR_KMAX || threadIdx.x == IR_VMAX)
-            atomicMax(&red[threadIdx.x], v);
-        else if (v)
-            atomicAdd(&red[threadIdx.x], v);
-    }
+    red_fold(s_red, red, IR_NSEG + 1, IR_WORDS - IR_NSEG - 1, IR_MIN_MASK, IR_MAX_MASK);
 }
 
 /* segments of up to lane_max ops: one lane each */
@@ -4784,15 +4779,11 @@ __global__ void __launch_bounds__(BLOCK)
     }
 }
 
-/* head flags and, after the caller's launch_psum of them into d_hrank, the
- * segment starts.  d_red: IR_WORDS u64 words, initialised here. */
-void launch_incr_heads(const WbKeys &k, uint64_t n, const uint64_t *d_w, const uint32_t *d_ix,
-                       uint64_t *d_head, uint64_t *d_red, hipStream_t s)
+void launch_key_heads(const WbKeys &k, uint64_t n, const uint64_t *d_w, const uint32_t *d_ix,
+                      uint64_t *d_head, uint64_t *d_red, int words, uint32_t min_mask,
+                      hipStream_t s)
 {
-    uint64_t init[IR_WORDS];
-    for (int j = 0; j < IR_WORDS; j++)
-        init[j] = (j == IR_KMIN || j == IR_VMIN) ? ~0ull : 0ull;
-    HIP_CHECK(hipMemcpyAsync(d_red, init, sizeof(init), hipMemcpyHostToDevice, s));
+    red_init(d_red, words, min_mask, s);
     k_incr_heads<<<grid_for(n, BLOCK), BLOCK, 0, s>>>(k, n, d_w, d_ix, d_head);
 }
 
@@ -4803,8 +4794,6 @@ void launch_incr_segs(uint64_t n, const uint64_t *d_head, const uint64_t *d_hran
                                                     (unsigned long long *)d_red);
 }
 
-/* both chain kernels; the segment count is read on the device, so the grids
- * are sized by the op count, which bounds it */
 void launch_incr_chain(const IncrArgs &a, hipStream_t s)
 {
     k_incr_chain_lane<<<grid_for(a.n, BLOCK), BLOCK, 0, s>>>(a);
@@ -5016,9 +5005,7 @@ __device__ static void cas_op(const CasArgs &a, uint32_t i, CasTally &t)
 __device__ static inline void cas_tally_flush(const CasTally &t, unsigned long long *s_red,
                                               unsigned long long *red)
 {
-    if (threadIdx.x < CR_WORDS)
-        s_red[threadIdx.x] = 0;
-    __syncthreads();
+    red_lds_init(s_red, CR_WORDS, CR_MIN_MASK);
     if (t.passed)
         atomicAdd(&s_red[CR_PASSED], t.passed);
     if (t.fcheck)
@@ -5031,9 +5018,7 @@ __device__ static inline void cas_tally_flush(const CasTally &t, unsigned long l
         atomicAdd(&s_red[CR_APPLIED], t.applied);
     if (t.retbytes)
         atomicAdd(&s_red[CR_RETBYTES], t.retbytes);
-    __syncthreads();
-    if (threadIdx.x >= CR_PASSED && threadIdx.x <= CR_RETBYTES && s_red[threadIdx.x])
-        atomicAdd(&red[threadIdx.x], s_red[threadIdx.x]);
+    red_fold(s_red, red, CR_PASSED, CR_RETBYTES - CR_PASSED + 1, CR_MIN_MASK, CR_MAX_MASK);
 }
 
 /* one lane per hashkey group, its ops oldest to newest */
@@ -5062,12 +5047,7 @@ __global__ void __launch_bounds__(BLOCK)
     k_cas_rows(CasArgs a, uint64_t *row, uint64_t *ksz, uint64_t *vsz)
 {
     __shared__ unsigned long long s_red[CR_WORDS];
-    if (threadIdx.x < CR_WORDS)
-        s_red[threadIdx.x] = (threadIdx.x == CR_KMIN || threadIdx.x == CR_VMIN ||
-                              threadIdx.x == CR_PVMIN)
-                                 ? ~0ull
-                                 : 0ull;
-    __syncthreads();
+    red_lds_init(s_red, CR_WORDS, CR_MIN_MASK);
     unsigned long long nout = 0, puts = 0, kb = 0, vb = 0, kmin = ~0ull, kmax = 0, vmin = ~0ull,
                        vmax = 0, pvmin = ~0ull, pvmax = 0;
     for (uint64_t p = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; p < a.E;
@@ -5110,16 +5090,7 @@ __global__ void __launch_bounds__(BLOCK)
             atomicMax(&s_red[CR_PVMAX], pvmax);
         }
     }
-    __syncthreads();
-    if (threadIdx.x >= CR_NOUT && threadIdx.x < CR_WORDS) {
-        const unsigned long long v = s_red[threadIdx.x];
-        if (threadIdx.x == CR_KMIN || threadIdx.x == CR_VMIN || threadIdx.x == CR_PVMIN)
-            atomicMin(&a.red[threadIdx.x], v);
-        else if (threadIdx.x == CR_KMAX || threadIdx.x == CR_VMAX || threadIdx.x == CR_PVMAX)
-            atomicMax(&a.red[threadIdx.x], v);
-        else if (v)
-            atomicAdd(&a.red[threadIdx.x], v);
-    }
+    red_fold(s_red, a.red, CR_NOUT, CR_WORDS - CR_NOUT, CR_MIN_MASK, CR_MAX_MASK);
 }
 
 /* the rows, by rank: osk, 0-based okoff/ovoff (n_out+1 entries) and the
@@ -5152,21 +5123,14 @@ __global__ void __launch_bounds__(BLOCK)
     }
 }
 
-/* head flags and the inverse permutation.  d_red: CR_WORDS u64 words,
- * initialised here. */
 void launch_cas_heads(const WbKeys &k, uint64_t E, const uint64_t *d_w, const uint32_t *d_ix,
                       uint8_t *d_khead, uint64_t *d_hhead, uint32_t *d_pos, uint64_t *d_red,
                       hipStream_t s)
 {
-    uint64_t init[CR_WORDS];
-    for (int j = 0; j < CR_WORDS; j++)
-        init[j] = (j == CR_KMIN || j == CR_VMIN || j == CR_PVMIN) ? ~0ull : 0ull;
-    HIP_CHECK(hipMemcpyAsync(d_red, init, sizeof(init), hipMemcpyHostToDevice, s));
+    red_init(d_red, CR_WORDS, CR_MIN_MASK, s);
     k_cas_heads<<<grid_for(E, BLOCK), BLOCK, 0, s>>>(k, E, d_w, d_ix, d_khead, d_hhead, d_pos);
 }
 
-/* after the caller's launch_psum of d_hhead into d_hrank: the words the
- * second sort orders the ops by */
 void launch_cas_group_words(uint64_t n, uint64_t E, const uint64_t *d_moff, const uint32_t *d_pos,
                             const uint64_t *d_hhead, const uint64_t *d_hrank, uint8_t *d_words,
                             uint64_t *d_red, hipStream_t s)
@@ -5181,8 +5145,6 @@ void launch_cas_segs(uint64_t n, const uint8_t *d_words, const uint32_t *d_ops,
     k_cas_segs<<<grid_for(n, BLOCK), BLOCK, 0, s>>>(n, d_words, d_ops, d_seg_start);
 }
 
-/* the group count is read on the device, so the grid is sized by the op
- * count, which bounds it */
 void launch_cas_walk(const CasArgs &a, hipStream_t s)
 {
     k_cas_walk_lane<<<grid_for(a.n, BLOCK), BLOCK, 0, s>>>(a);
@@ -5301,22 +5263,11 @@ __device__ static void wbt_walk(const TtArgs &a, uint64_t s, uint64_t beg, uint6
     wbt_seg_out(a, s, last, t);
 }
 
-__device__ static inline bool wbt_is_min(int w)
-{
-    return w == TR_KMIN || w == TR_VMIN || w == TR_PVMIN;
-}
-__device__ static inline bool wbt_is_max(int w)
-{
-    return w == TR_KMAX || w == TR_VMAX || w == TR_PVMAX;
-}
-
 /* block-level then device-level fold of the per-thread tallies */
 __device__ static inline void wbt_tally_flush(const TtTally &t, unsigned long long *s_red,
                                               unsigned long long *red)
 {
-    if (threadIdx.x < TR_WORDS)
-        s_red[threadIdx.x] = wbt_is_min(threadIdx.x) ? ~0ull : 0ull;
-    __syncthreads();
+    red_lds_init(s_red, TR_WORDS, TR_MIN_MASK);
     if (t.applied)
         atomicAdd(&s_red[TR_APPLIED], t.applied);
     if (t.ignored)
@@ -5335,16 +5286,7 @@ __device__ static inline void wbt_tally_flush(const TtTally &t, unsigned long lo
             atomicMax(&s_red[TR_PVMAX], t.pvmax);
         }
     }
-    __syncthreads();
-    if (threadIdx.x > TR_NSEG && threadIdx.x < TR_WORDS) {
-        const unsigned long long v = s_red[threadIdx.x];
-        if (wbt_is_min(threadIdx.x))
-            atomicMin(&red[threadIdx.x], v);
-        else if (wbt_is_max(threadIdx.x))
-            atomicMax(&red[threadIdx.x], v);
-        else if (v)
-            atomicAdd(&red[threadIdx.x], v);
-    }
+    red_fold(s_red, red, TR_NSEG + 1, TR_WORDS - TR_NSEG - 1, TR_MIN_MASK, TR_MAX_MASK);
 }
 
 /* segments of up to lane_max ops: one lane each */
@@ -5500,20 +5442,6 @@ __global__ void __launch_bounds__(BLOCK)
     }
 }
 
-/* head flags (the incr batch's kernel).  d_red: TR_WORDS u64 words,
- * initialised here; launch_psum and launch_incr_segs follow. */
-void launch_wbt_heads(const WbKeys &k, uint64_t n, const uint64_t *d_w, const uint32_t *d_ix,
-                      uint64_t *d_head, uint64_t *d_red, hipStream_t s)
-{
-    uint64_t init[TR_WORDS];
-    for (int j = 0; j < TR_WORDS; j++)
-        init[j] = (j == TR_KMIN || j == TR_VMIN || j == TR_PVMIN) ? ~0ull : 0ull;
-    HIP_CHECK(hipMemcpyAsync(d_red, init, sizeof(init), hipMemcpyHostToDevice, s));
-    k_incr_heads<<<grid_for(n, BLOCK), BLOCK, 0, s>>>(k, n, d_w, d_ix, d_head);
-}
-
-/* both walk kernels; the segment count is read on the device, so the grids
- * are sized by the op count, which bounds it */
 void launch_wbt_walk(const TtArgs &a, hipStream_t s)
 {
     k_wbt_walk_lane<<<grid_for(a.n, BLOCK), BLOCK, 0, s>>>(a);
