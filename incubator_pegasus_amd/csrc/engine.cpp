@@ -525,11 +525,26 @@ static uint32_t shared_stride(const RunBuf *wr, int R, uint32_t RunBuf::*f)
     return R ? wr[0].*f : 0;
 }
 
+/* build_view's result, a range's visible record ids in key order: a plain device
+ * allocation (a parked scan keeps it), move-only, freed on every way out */
+struct DevView {
+    uint64_t *d = nullptr;
+    uint64_t n = 0;
+    DevView() = default;
+    DevView(uint64_t *d_, uint64_t n_) : d(d_), n(n_) {}
+    DevView(DevView &&o) noexcept : d(o.d), n(o.n) { o.d = nullptr, o.n = 0; }
+    DevView &operator=(DevView &&o) noexcept
+    {
+        std::swap(d, o.d), std::swap(n, o.n);
+        return *this;
+    }
+    ~DevView() { if (d) (void)hipFree(d); }
+};
+
 struct HipScanCtx {
     int64_t id = 0;
     uint32_t parked_at = 0; /* epoch_now when (re-)parked; 5-min GC */
-    uint64_t *d_view = nullptr;
-    uint64_t view_n = 0;
+    DevView view;
     uint64_t cursor = 0;
     int32_t batch_size = -1;
     uint8_t no_value = 0, validate_hash_req = 1, return_expire_ts = 0, only_return_count = 0,
@@ -541,8 +556,6 @@ struct HipScanCtx {
     uint64_t sk_pat_len = 0;
     ~HipScanCtx()
     {
-        if (d_view)
-            (void)hipFree(d_view);
         if (d_hk_pat)
             (void)hipFree(d_hk_pat);
         if (d_sk_pat)
@@ -1353,8 +1366,6 @@ struct HipEngine {
         memcpy(dst, pb, n);
     }
 
-    /* build the visible view for [start, stop_excl); returns device array
-     * (caller frees) + count */
     /* group-streaming rank: pick the anchor run (largest window) and stride,
      * build the anchor table (arena memory).  Returns n_groups. */
     uint64_t build_anchors(DevRun *dr, int R, const std::vector<uint64_t> &lo,
@@ -1380,15 +1391,13 @@ struct HipEngine {
         return n_groups;
     }
 
-    void build_view(const std::string *start, const std::string *stop_excl, uint64_t **out_view,
-                    uint64_t *out_n)
+    /* build the visible view for [start, stop_excl); a null bound is open */
+    DevView build_view(const std::string *start, const std::string *stop_excl)
     {
         int R = (int)runs.size();
-        *out_view = nullptr;
-        *out_n = 0;
         last_view = rrdb_view_route{RRDB_ROUTE_NONE, 0, 0, 0, 0};
         if (R == 0)
-            return;
+            return {};
         DevRun *dr = dev_runs();
         uint64_t *d_lo = talloc<uint64_t>(R * 8);
         uint64_t *d_hi = talloc<uint64_t>(R * 8);
@@ -1415,7 +1424,7 @@ struct HipEngine {
         if (total == 0) {
             tfree(d_lo);
             tfree(d_hi);
-            return;
+            return {};
         }
         /* re-upload corrected hi + wprefix */
         HIP_OK(hipMemcpy(d_hi, hi.data(), R * 8, hipMemcpyHostToDevice));
@@ -1468,8 +1477,7 @@ struct HipEngine {
         tfree(d_flags);
         tfree(d_pos);
         HIP_OK(hipStreamSynchronize(stream));
-        *out_view = d_view;
-        *out_n = nv;
+        return DevView(d_view, nv);
     }
 };
 
@@ -1921,46 +1929,156 @@ int32_t rrdb_ttl(void *h, const uint8_t *key, uint64_t key_len, uint32_t epoch_n
     return out->error;
 }
 
-/* ---- scan machinery shared by scan/sortkey_count/multi_get-range ---- */
+} /* extern "C" */
 
-struct BatchOut {
-    uint64_t consumed = 0;  /* view entries consumed */
-    uint64_t n_out = 0;     /* normal rows */
+/* ---- what the read entry points below share; what a path does differently
+ * stays written out in its function.  DevView is up with HipScanCtx. ---- */
+namespace {
+
+/* flush, fresh scratch and result.  Null: the flush failed (device full; writes
+ * retained), *out says kIOError.  activate() is the caller's: it may validate first. */
+Arena *read_begin(HipEngine *e, rrdb_result *out)
+{
+    if (engine_flush(e) != RRDB_OK) {
+        result_init(out);
+        out->error = RRDB_IO_ERROR;
+        return nullptr;
+    }
+    e->scratch_reset();
+    return result_init(out);
+}
+
+/* a key range: a builder sets the ends and clamps them by a prefix filter,
+ * close() finishes it; what an empty range returns is the caller's business */
+struct KeyRange {
+    std::string start, stop;
+    std::string stop_excl; /* smallest key past the range: what the kernels take */
+    bool start_inclusive = true, stop_inclusive = false;
+    void clamp_start(const std::string &ps)
+    {
+        if (key_cmp(ps, start) > 0)
+            start = ps, start_inclusive = true;
+    }
+    /* false: the range is empty (on_get_scanner:1227-1243, on_multi_get:580-607) */
+    bool close()
+    {
+        int c = key_cmp(start, stop);
+        if (c > 0 || (c == 0 && (!start_inclusive || !stop_inclusive)))
+            return false;
+        stop_excl = stop;
+        if (stop_inclusive)
+            stop_excl.push_back('\0');
+        return true;
+    }
 };
 
-/* run one forward batch over ctx->d_view[cursor..]; emits into result */
-static void scan_batch_gpu(HipEngine *e, HipScanCtx *c, uint32_t epoch_now, rrdb_result *out,
-                           Arena *a)
+/* scan: the request's keys; a hash-key prefix filter clamps start only
+ * (on_get_scanner:1206-1224).  The caller has checked the pattern's length. */
+KeyRange scan_range(const rrdb_scan_request *q)
 {
-    auto t_start = std::chrono::steady_clock::now();
-    uint32_t batch_count = e->max_iter_count;
-    if (c->batch_size > 0 && (uint32_t)c->batch_size < batch_count)
-        batch_count = (uint32_t)c->batch_size;
-    uint64_t remaining = c->view_n - c->cursor;
-    uint64_t w = std::min<uint64_t>(remaining, e->max_iter_count);
-    if (w == 0) {
-        out->error = RRDB_OK;
-        out->context_id = RRDB_SCAN_CONTEXT_ID_COMPLETED;
-        if (c->only_return_count) {
-            out->i64 = 0;
-        } else {
-            /* a normal zero-row batch returns allocated (empty) arrays —
-             * only the empty-RANGE early return leaves them null (matches
-             * the oracle's scan_batch, observable via expire_ts) */
-            out->keys = (rrdb_slice *)a->alloc(sizeof(rrdb_slice));
-            out->values = (rrdb_slice *)a->alloc(sizeof(rrdb_slice));
-            if (c->return_expire_ts)
-                out->expire_ts = (int32_t *)a->alloc(4);
-        }
-        return;
+    KeyRange kr;
+    kr.start.assign((const char *)q->start_key.data, q->start_key.len);
+    kr.stop.assign((const char *)q->stop_key.data, q->stop_key.len);
+    kr.start_inclusive = q->start_inclusive;
+    kr.stop_inclusive = q->stop_inclusive;
+    if (q->hash_key_filter_type == RRDB_FT_MATCH_PREFIX && q->hash_key_filter_pattern.len > 0)
+        kr.clamp_start(
+            make_key(q->hash_key_filter_pattern.data, q->hash_key_filter_pattern.len, nullptr, 0));
+    return kr;
+}
+
+/* all of one hash key: start=(hk,""), stop=next(hk) (on_sortkey_count:1030-1036) */
+KeyRange hash_key_range(const uint8_t *hk, uint64_t hklen)
+{
+    KeyRange kr;
+    kr.start = make_key(hk, hklen, nullptr, 0);
+    kr.stop = next_blob(kr.start);
+    return kr;
+}
+
+/* multi_get's range (on_multi_get:542-578): sort-key bounds in one hash key, an
+ * empty stop being the hash key's end; a sort-key prefix filter clamps both ends */
+KeyRange mg_range(const rrdb_multi_get_request *q)
+{
+    const uint8_t *hk = q->hash_key.data;
+    const uint64_t hklen = q->hash_key.len;
+    KeyRange kr = hash_key_range(hk, hklen);
+    kr.start = make_key(hk, hklen, q->start_sortkey.data, q->start_sortkey.len);
+    kr.start_inclusive = q->start_inclusive;
+    if (q->stop_sortkey.len != 0) {
+        kr.stop = make_key(hk, hklen, q->stop_sortkey.data, q->stop_sortkey.len);
+        kr.stop_inclusive = q->stop_inclusive;
     }
-    DevRun *dr = e->dev_runs();
-    const uint64_t *d_win = c->d_view + c->cursor;
+    if (q->sort_key_filter_type == RRDB_FT_MATCH_PREFIX && q->sort_key_filter_pattern.len > 0) {
+        std::string ps =
+            make_key(hk, hklen, q->sort_key_filter_pattern.data, q->sort_key_filter_pattern.len);
+        kr.clamp_start(ps);
+        if (std::string pe = next_blob(ps); key_cmp(pe, kr.stop) <= 0)
+            kr.stop = pe, kr.stop_inclusive = false;
+    }
+    return kr;
+}
+
+/* is the record at this view position exactly `bound`?  One launch, one host sync. */
+bool key_at_equals(HipEngine *e, const uint64_t *d_view_pos, const std::string &bound)
+{
+    uint32_t *d_eq = e->talloc<uint32_t>(4);
+    uint8_t *d_b = e->upload_tmp(bound.data(), bound.size());
+    launch_first_eq(e->dev_runs(), d_view_pos, 1, d_b, bound.size(), d_eq, e->stream);
+    uint32_t eq = 0;
+    HIP_OK(hipMemcpyAsync(&eq, d_eq, 4, hipMemcpyDeviceToHost, e->stream));
+    HIP_OK(hipStreamSynchronize(e->stream));
+    e->tfree(d_eq);
+    e->tfree(d_b);
+    return eq != 0;
+}
+
+/* the engine's part of a ScanParams; the rest starts zero */
+ScanParams base_scan_params(const HipEngine *e, uint32_t epoch_now)
+{
     ScanParams sp{};
     sp.epoch_now = epoch_now;
     sp.data_version = e->data_version;
     sp.pidx = e->pidx;
     sp.partition_version = e->partition_version;
+    return sp;
+}
+
+/* multi_get's limits (on_multi_get:523-533): the request's, capped by the engine's */
+struct MgLimits {
+    uint32_t max_kv_count, max_iteration_count;
+    int64_t max_kv_size, max_iter_size;
+    MgLimits(const HipEngine *e, const rrdb_multi_get_request *q)
+    {
+        max_kv_count = max_iteration_count = e->mg_max_iter_count;
+        if (q->max_kv_count > 0 && (uint32_t)q->max_kv_count < max_kv_count)
+            max_kv_count = (uint32_t)q->max_kv_count;
+        max_kv_size = q->max_kv_size > 0 ? q->max_kv_size : INT32_MAX;
+        max_iter_size = std::min<int64_t>(
+            max_kv_size, e->mg_max_iter_size > 0 ? (int64_t)e->mg_max_iter_size : INT32_MAX);
+    }
+};
+
+} // namespace
+
+extern "C" {
+
+/* ---- scan machinery shared by scan/sortkey_count/multi_get-range ---- */
+
+/* a zero-row batch returns allocated (empty) arrays: only the empty-RANGE early
+ * return leaves them null (matches the oracle's scan_batch, observable via expire_ts) */
+static void scan_empty_rows(const HipScanCtx *c, rrdb_result *out, Arena *a)
+{
+    out->keys = (rrdb_slice *)a->alloc(sizeof(rrdb_slice));
+    out->values = (rrdb_slice *)a->alloc(sizeof(rrdb_slice));
+    if (c->return_expire_ts)
+        out->expire_ts = (int32_t *)a->alloc(4);
+}
+
+/* the filters and flags a scan context carries, as the kernels take them */
+static ScanParams ctx_scan_params(const HipEngine *e, const HipScanCtx *c, uint32_t epoch_now)
+{
+    ScanParams sp = base_scan_params(e, epoch_now);
     sp.validate_hash = (uint8_t)(c->validate_hash_req && e->validate_hash);
     sp.hk_ft = c->hk_ft;
     sp.sk_ft = c->sk_ft;
@@ -1969,8 +2087,31 @@ static void scan_batch_gpu(HipEngine *e, HipScanCtx *c, uint32_t epoch_now, rrdb
     sp.sk_pat = c->d_sk_pat;
     sp.sk_pat_len = c->sk_pat_len;
     sp.no_value = c->no_value;
-    sp.hash_key_skip = 0;
+    return sp;
+}
 
+/* run one forward batch over ctx->view[cursor..]; emits into result */
+static void scan_batch_gpu(HipEngine *e, HipScanCtx *c, uint32_t epoch_now, rrdb_result *out,
+                           Arena *a)
+{
+    auto t_start = std::chrono::steady_clock::now();
+    uint32_t batch_count = e->max_iter_count;
+    if (c->batch_size > 0 && (uint32_t)c->batch_size < batch_count)
+        batch_count = (uint32_t)c->batch_size;
+    uint64_t remaining = c->view.n - c->cursor;
+    uint64_t w = std::min<uint64_t>(remaining, e->max_iter_count);
+    if (w == 0) {
+        out->error = RRDB_OK;
+        out->context_id = RRDB_SCAN_CONTEXT_ID_COMPLETED;
+        if (c->only_return_count)
+            out->i64 = 0;
+        else
+            scan_empty_rows(c, out, a);
+        return;
+    }
+    DevRun *dr = e->dev_runs();
+    const uint64_t *d_win = c->view.d + c->cursor;
+    const ScanParams sp = ctx_scan_params(e, c, epoch_now);
     uint8_t *d_state = e->talloc<uint8_t>(w);
     uint64_t *d_ksz = e->talloc<uint64_t>(w * 8);
     uint64_t *d_vsz = e->talloc<uint64_t>(w * 8);
@@ -1996,10 +2137,7 @@ static void scan_batch_gpu(HipEngine *e, HipScanCtx *c, uint32_t epoch_now, rrdb
         out->count = 0;
     } else if (n_out == 0) {
         out->count = 0;
-        out->keys = (rrdb_slice *)a->alloc(sizeof(rrdb_slice));
-        out->values = (rrdb_slice *)a->alloc(sizeof(rrdb_slice));
-        if (c->return_expire_ts)
-            out->expire_ts = (int32_t *)a->alloc(4);
+        scan_empty_rows(c, out, a);
     } else {
         launch_cut_sizes(d_state, w, consumed, d_ksz, d_vsz, e->stream);
         uint64_t *d_koffs = e->talloc<uint64_t>(w * 8);
@@ -2095,7 +2233,7 @@ static void scan_batch_gpu(HipEngine *e, HipScanCtx *c, uint32_t epoch_now, rrdb
     c->cursor += consumed;
     out->error = RRDB_OK;
     out->context_id =
-        (c->cursor >= c->view_n) ? RRDB_SCAN_CONTEXT_ID_COMPLETED : 0 /* caller parks */;
+        (c->cursor >= c->view.n) ? RRDB_SCAN_CONTEXT_ID_COMPLETED : 0 /* caller parks */;
     /* time budget (range_read_limiter.h:56-79), batch granularity: an
      * over-budget incomplete batch returns kIncomplete, no re-park */
     if (out->context_id != RRDB_SCAN_CONTEXT_ID_COMPLETED && e->iter_time_ms > 0) {
@@ -2112,14 +2250,10 @@ static void scan_batch_gpu(HipEngine *e, HipScanCtx *c, uint32_t epoch_now, rrdb
 int32_t rrdb_scan_open(void *h, const rrdb_scan_request *q, uint32_t epoch_now, rrdb_result *out)
 {
     auto *e = (HipEngine *)h;
-    std::lock_guard<std::mutex> g(((HipEngine *)h)->mu);
-    if (engine_flush((HipEngine *)h) != RRDB_OK) {
-        result_init(out);
-        out->error = RRDB_IO_ERROR; /* device full; writes retained */
+    std::lock_guard<std::mutex> g(e->mu);
+    Arena *a = read_begin(e, out);
+    if (!a)
         return out->error;
-    }
-    ((HipEngine *)h)->scratch_reset();
-    Arena *a = result_init(out);
     if (q->hash_key_filter_type < 0 || q->hash_key_filter_type > 3 ||
         q->sort_key_filter_type < 0 || q->sort_key_filter_type > 3 ||
         (q->hash_key_filter_type == RRDB_FT_MATCH_PREFIX &&
@@ -2128,43 +2262,17 @@ int32_t rrdb_scan_open(void *h, const rrdb_scan_request *q, uint32_t epoch_now, 
         return out->error;
     }
     e->activate();
-    std::string start((const char *)q->start_key.data, q->start_key.len);
-    std::string stop((const char *)q->stop_key.data, q->stop_key.len);
-    bool start_inclusive = q->start_inclusive, stop_inclusive = q->stop_inclusive;
-    /* hash-key prefix filter clamps start (on_get_scanner:1206-1224) */
-    if (q->hash_key_filter_type == RRDB_FT_MATCH_PREFIX && q->hash_key_filter_pattern.len > 0) {
-        std::string ps =
-            make_key(q->hash_key_filter_pattern.data, q->hash_key_filter_pattern.len, nullptr, 0);
-        if (key_cmp(ps, start) > 0) {
-            start = ps;
-            start_inclusive = true;
-        }
-    }
-    int c = key_cmp(start, stop);
-    if (c > 0 || (c == 0 && (!start_inclusive || !stop_inclusive))) {
-        out->error = RRDB_OK; /* empty range (on_get_scanner:1227-1243) */
+    KeyRange kr = scan_range(q);
+    if (!kr.close()) {
+        out->error = RRDB_OK; /* empty range: the arrays stay null */
         out->context_id = RRDB_SCAN_CONTEXT_ID_COMPLETED;
         return RRDB_OK;
     }
     auto *ctx = new HipScanCtx();
-    std::string stop_excl = stop;
-    if (stop_inclusive)
-        stop_excl.push_back('\0'); /* smallest key > stop */
-    e->build_view(&start, &stop_excl, &ctx->d_view, &ctx->view_n);
+    ctx->view = e->build_view(&kr.start, &kr.stop_excl);
     /* first_exclusive: skip an exact start match (on_get_scanner:1277-1283) */
-    if (!start_inclusive && ctx->view_n > 0) {
-        uint32_t *d_eq = e->talloc<uint32_t>(4);
-        uint8_t *d_sk = e->upload_tmp(start.data(), start.size());
-        launch_first_eq(e->dev_runs(), ctx->d_view, ctx->view_n, d_sk, start.size(), d_eq,
-                        e->stream);
-        uint32_t eq = 0;
-        HIP_OK(hipMemcpyAsync(&eq, d_eq, 4, hipMemcpyDeviceToHost, e->stream));
-        HIP_OK(hipStreamSynchronize(e->stream));
-        e->tfree(d_eq);
-        e->tfree(d_sk);
-        if (eq)
-            ctx->cursor = 1;
-    }
+    if (!kr.start_inclusive && ctx->view.n > 0 && key_at_equals(e, ctx->view.d, kr.start))
+        ctx->cursor = 1;
     ctx->batch_size = q->batch_size;
     ctx->no_value = q->no_value;
     ctx->validate_hash_req = q->validate_partition_hash;
@@ -2262,28 +2370,20 @@ int32_t rrdb_scan_count_begin(void *h, const rrdb_scan_request *q, uint32_t epoc
         return RRDB_OK;
     }
 
-    std::string start((const char *)q->start_key.data, q->start_key.len);
-    std::string stop((const char *)q->stop_key.data, q->stop_key.len);
-    bool start_inclusive = true, stop_inclusive = q->stop_inclusive;
-    if (q->hash_key_filter_type == RRDB_FT_MATCH_PREFIX && q->hash_key_filter_pattern.len > 0) {
-        if (!hklen_ok(q->hash_key_filter_pattern.len))
-            return RRDB_INVALID_ARGUMENT;
-        std::string ps =
-            make_key(q->hash_key_filter_pattern.data, q->hash_key_filter_pattern.len, nullptr, 0);
-        if (key_cmp(ps, start) > 0)
-            start = ps;
-    }
-    int c = key_cmp(start, stop);
-    if (c > 0 || (c == 0 && (!start_inclusive || !stop_inclusive))) {
+    /* the pattern's length matters only where the prefix clamp uses it */
+    if (q->hash_key_filter_type == RRDB_FT_MATCH_PREFIX && q->hash_key_filter_pattern.len > 0 &&
+        !hklen_ok(q->hash_key_filter_pattern.len))
+        return RRDB_INVALID_ARGUMENT;
+    KeyRange kr = scan_range(q);
+    kr.start_inclusive = true; /* the request's, required above */
+    if (!kr.close()) {
         e->pend_scan.active = true;
         e->pend_scan.trivial = true;
         e->pend_scan.trivial_count = 0;
-        return RRDB_OK; /* empty range (on_get_scanner:1227-1243) */
+        return RRDB_OK; /* empty range */
     }
     e->pend_scan.trivial = false;
-    std::string stop_excl = stop;
-    if (stop_inclusive)
-        stop_excl.push_back('\0');
+    const std::string &start = kr.start, &stop_excl = kr.stop_excl;
 
     int R = (int)e->runs.size();
     DevRun *dr = e->dev_runs();
@@ -2344,11 +2444,7 @@ int32_t rrdb_scan_count_begin(void *h, const rrdb_scan_request *q, uint32_t epoc
         launch_anchor_rows(dr, R, q0, ps.d_lo, ps.d_hi, gs, n_groups, ps.d_anch, e->stream);
     }
 
-    ScanParams sp{};
-    sp.epoch_now = epoch_now;
-    sp.data_version = e->data_version;
-    sp.pidx = e->pidx;
-    sp.partition_version = e->partition_version;
+    ScanParams sp = base_scan_params(e, epoch_now);
     sp.validate_hash = (uint8_t)(q->validate_partition_hash && e->validate_hash);
     sp.hk_ft = q->hash_key_filter_type;
     sp.sk_ft = q->sort_key_filter_type;
@@ -2357,7 +2453,6 @@ int32_t rrdb_scan_count_begin(void *h, const rrdb_scan_request *q, uint32_t epoc
     sp.sk_pat_len = q->sort_key_filter_pattern.len;
     sp.sk_pat = upl(q->sort_key_filter_pattern.data, q->sort_key_filter_pattern.len);
     sp.no_value = 1;
-    sp.hash_key_skip = 0;
 
     if (!ps.d_stats)
         HIP_OK(hipMalloc(&ps.d_stats, 8 * sizeof(CompactStatsDev)));
@@ -2420,40 +2515,30 @@ int32_t rrdb_sortkey_count(void *h, const uint8_t *hash_key, uint64_t hklen, uin
                            rrdb_result *out)
 {
     auto *e = (HipEngine *)h;
-    std::lock_guard<std::mutex> g(((HipEngine *)h)->mu);
-    if (engine_flush((HipEngine *)h) != RRDB_OK) {
-        result_init(out);
-        out->error = RRDB_IO_ERROR;
+    std::lock_guard<std::mutex> g(e->mu);
+    if (!read_begin(e, out))
         return out->error;
-    }
-    ((HipEngine *)h)->scratch_reset();
-    result_init(out);
     e->activate();
     if (!hklen_ok(hklen)) {
         out->error = RRDB_INVALID_ARGUMENT;
         return out->error;
     }
-    /* start=(hk,""), stop=next(hk) (on_sortkey_count:1030-1036); count all
-     * visible non-expired rows — no count cap in the reference's loop */
-    std::string start = make_key(hash_key, hklen, nullptr, 0);
-    std::string stop = next_blob(start);
-    uint64_t *d_view = nullptr, n = 0;
-    e->build_view(&start, &stop, &d_view, &n);
+    /* count all visible non-expired rows of the hash key — no count cap in
+     * the reference's loop */
+    KeyRange kr = hash_key_range(hash_key, hklen);
+    (void)kr.close(); /* never empty (start < next(start)); called for stop_excl */
+    DevView view = e->build_view(&kr.start, &kr.stop_excl);
+    const uint64_t n = view.n;
     int64_t count = 0;
     if (n) {
-        DevRun *dr = e->dev_runs();
-        ScanParams sp{};
-        sp.epoch_now = epoch_now;
-        sp.data_version = e->data_version;
-        sp.pidx = e->pidx;
-        sp.partition_version = e->partition_version;
-        sp.validate_hash = 0;
+        /* no hash validation, no filter */
+        ScanParams sp = base_scan_params(e, epoch_now);
         uint8_t *d_state = e->talloc<uint8_t>(n);
         uint64_t *d_ksz = e->talloc<uint64_t>(n * 8);
         uint64_t *d_vsz = e->talloc<uint64_t>(n * 8);
         uint64_t *d_flags = e->talloc<uint64_t>(n * 8);
         uint64_t *d_npos = e->talloc<uint64_t>(n * 8);
-        launch_scan_state(dr, d_view, n, sp, d_state, d_ksz, d_vsz, e->stream);
+        launch_scan_state(e->dev_runs(), view.d, n, sp, d_state, d_ksz, d_vsz, e->stream);
         launch_normal_flags(d_state, n, d_flags, e->stream);
         launch_psum(d_flags, d_npos, n, e->psum_scratch(n), e->stream);
         uint64_t lastp = 0, lastf = 0;
@@ -2467,14 +2552,11 @@ int32_t rrdb_sortkey_count(void *h, const uint8_t *hash_key, uint64_t hklen, uin
         e->tfree(d_flags);
         e->tfree(d_npos);
     }
-    if (d_view)
-        (void)hipFree(d_view);
     out->i64 = count;
     out->error = RRDB_OK;
     return RRDB_OK;
 }
 
-/* body of on_multi_get; caller holds the engine lock */
 /* bounded busy-wait completion for the small-op serving path: the blocking
  * stream sync costs ~10-20us of wakeup latency per call */
 static inline void spin_sync(hipStream_t st)
@@ -2510,335 +2592,249 @@ static bool valid_beyond(HipEngine *e, const std::string &bound, bool reverse)
         return v != 0;
     }
     /* > RRDB_MAX_RUNS runs: fall back to a visible-view existence check */
-    uint64_t *d_view = nullptr, n = 0;
-    std::string b = bound;
-    if (!reverse)
-        e->build_view(&b, nullptr, &d_view, &n);
-    else
-        e->build_view(nullptr, &b, &d_view, &n);
-    if (d_view)
-        (void)hipFree(d_view);
-    return n != 0;
+    return (reverse ? e->build_view(nullptr, &bound) : e->build_view(&bound, nullptr)).n != 0;
 }
 
-static int32_t multi_get_locked(void *h, const rrdb_multi_get_request *q, uint32_t epoch_now,
-                                rrdb_result *out, rrdb_multi_get_lane *rep)
+/* the three bodies of multi_get, dispatched by multi_get_locked below them;
+ * rep is the call's lane report, only ever written */
+
+/* point-list variant (on_multi_get:779-860) over the batched-get core */
+static int32_t mg_point_list(HipEngine *e, const rrdb_multi_get_request *q, const MgLimits &lim,
+                             uint32_t epoch_now, rrdb_result *out, Arena *a)
 {
-    auto *e = (HipEngine *)h;
-    /* rep: the lane report of this call (a batch's per-request fallbacks
-     * hand in a scratch one); only ever written */
-    rep->lane = RRDB_MG_LANE_NONE;
-    rep->fused_first = RRDB_MG_LANE_NONE;
-    rep->tail_read = 0;
-    if (engine_flush(e) != RRDB_OK) {
-        result_init(out);
-        out->error = RRDB_IO_ERROR;
-        return out->error;
+    std::vector<uint64_t> offs(q->n_sort_keys + 1);
+    std::string keys;
+    for (uint64_t i = 0; i < q->n_sort_keys; i++) {
+        offs[i] = keys.size();
+        keys += make_key(q->hash_key.data, q->hash_key.len, q->sort_keys + q->sort_key_offs[i],
+                         q->sort_key_offs[i + 1] - q->sort_key_offs[i]);
     }
-    e->scratch_reset();
-    Arena *a = result_init(out);
-    e->activate();
-    if (q->sort_key_filter_type < 0 || q->sort_key_filter_type > 3 ||
-        !hklen_ok(q->hash_key.len)) {
-        out->error = RRDB_INVALID_ARGUMENT; /* on_multi_get:508-517 */
-        return out->error;
+    offs[q->n_sort_keys] = keys.size();
+    std::vector<int32_t> status;
+    std::vector<std::pair<const uint8_t *, uint64_t>> vals;
+    get_core(e, q->n_sort_keys, (const uint8_t *)keys.data(), offs.data(), epoch_now, status,
+             vals, a);
+    out->keys = (rrdb_slice *)a->alloc(q->n_sort_keys * sizeof(rrdb_slice));
+    out->values = (rrdb_slice *)a->alloc(q->n_sort_keys * sizeof(rrdb_slice));
+    uint64_t m = 0;
+    int64_t count = 0, size = 0;
+    bool exceed = false;
+    for (uint64_t i = 0; i < q->n_sort_keys; i++) {
+        if (status[i] != RRDB_OK)
+            continue;
+        if (count >= (int64_t)lim.max_kv_count || size >= lim.max_kv_size) {
+            exceed = true; /* :837-841 */
+            break;
+        }
+        uint64_t sklen = q->sort_key_offs[i + 1] - q->sort_key_offs[i];
+        uint8_t *kc = (uint8_t *)a->alloc(sklen);
+        memcpy(kc, q->sort_keys + q->sort_key_offs[i], sklen);
+        out->keys[m] = {kc, sklen};
+        if (!q->no_value)
+            out->values[m] = {(uint8_t *)vals[i].first, vals[i].second};
+        else
+            out->values[m] = {nullptr, 0};
+        count++;
+        size += (int64_t)out->keys[m].len + (int64_t)out->values[m].len;
+        m++;
     }
-    uint32_t max_kv_count = e->mg_max_iter_count;
-    if (q->max_kv_count > 0 && (uint32_t)q->max_kv_count < max_kv_count)
-        max_kv_count = (uint32_t)q->max_kv_count;
-    int64_t max_kv_size = q->max_kv_size > 0 ? q->max_kv_size : INT32_MAX;
-    int64_t max_iter_size = std::min<int64_t>(
-        max_kv_size, e->mg_max_iter_size > 0 ? (int64_t)e->mg_max_iter_size : INT32_MAX);
-    uint32_t max_iteration_count = e->mg_max_iter_count;
+    out->count = m;
+    out->error = exceed ? RRDB_INCOMPLETE : RRDB_OK;
+    return out->error;
+}
 
-    if (q->n_sort_keys > 0) {
-        /* point-list variant (on_multi_get:779-860) over the batched-get core */
-        rep->lane = RRDB_MG_LANE_POINT_LIST;
-        std::vector<uint64_t> offs(q->n_sort_keys + 1);
-        std::string keys;
-        for (uint64_t i = 0; i < q->n_sort_keys; i++) {
-            offs[i] = keys.size();
-            keys += make_key(q->hash_key.data, q->hash_key.len,
-                             q->sort_keys + q->sort_key_offs[i],
-                             q->sort_key_offs[i + 1] - q->sort_key_offs[i]);
-        }
-        offs[q->n_sort_keys] = keys.size();
-        std::vector<int32_t> status;
-        std::vector<std::pair<const uint8_t *, uint64_t>> vals;
-        get_core(e, q->n_sort_keys, (const uint8_t *)keys.data(), offs.data(), epoch_now, status,
-                 vals, a);
-        out->keys = (rrdb_slice *)a->alloc(q->n_sort_keys * sizeof(rrdb_slice));
-        out->values = (rrdb_slice *)a->alloc(q->n_sort_keys * sizeof(rrdb_slice));
-        uint64_t m = 0;
-        int64_t count = 0, size = 0;
-        bool exceed = false;
-        for (uint64_t i = 0; i < q->n_sort_keys; i++) {
-            if (status[i] != RRDB_OK)
-                continue;
-            if (count >= (int64_t)max_kv_count || size >= max_kv_size) {
-                exceed = true; /* :837-841 */
-                break;
-            }
-            uint64_t sklen = q->sort_key_offs[i + 1] - q->sort_key_offs[i];
-            uint8_t *kc = (uint8_t *)a->alloc(sklen);
-            memcpy(kc, q->sort_keys + q->sort_key_offs[i], sklen);
-            out->keys[m] = {kc, sklen};
-            if (!q->no_value)
-                out->values[m] = {(uint8_t *)vals[i].first, vals[i].second};
-            else
-                out->values[m] = {nullptr, 0};
-            count++;
-            size += (int64_t)out->keys[m].len + (int64_t)out->values[m].len;
-            m++;
-        }
-        out->count = m;
-        out->error = exceed ? RRDB_INCOMPLETE : RRDB_OK;
-        return out->error;
-    }
-
-    /* range variant (on_multi_get:540-778) */
-    std::string start =
-        make_key(q->hash_key.data, q->hash_key.len, q->start_sortkey.data, q->start_sortkey.len);
-    std::string stop;
-    bool start_inclusive = q->start_inclusive, stop_inclusive;
-    if (q->stop_sortkey.len == 0) {
-        stop = next_blob(make_key(q->hash_key.data, q->hash_key.len, nullptr, 0));
-        stop_inclusive = false;
-    } else {
-        stop = make_key(q->hash_key.data, q->hash_key.len, q->stop_sortkey.data,
-                        q->stop_sortkey.len);
-        stop_inclusive = q->stop_inclusive;
-    }
-    if (q->sort_key_filter_type == RRDB_FT_MATCH_PREFIX && q->sort_key_filter_pattern.len > 0) {
-        std::string ps = make_key(q->hash_key.data, q->hash_key.len,
-                                  q->sort_key_filter_pattern.data, q->sort_key_filter_pattern.len);
-        std::string pe = next_blob(ps);
-        if (key_cmp(ps, start) > 0) {
-            start = ps;
-            start_inclusive = true;
-        }
-        if (key_cmp(pe, stop) <= 0) {
-            stop = pe;
-            stop_inclusive = false;
-        }
-    }
-    int c = key_cmp(start, stop);
-    if (c > 0 || (c == 0 && (!start_inclusive || !stop_inclusive))) {
-        out->error = RRDB_OK; /* empty range (:580-607) */
-        return RRDB_OK;
-    }
-    std::string stop_excl = stop;
-    if (stop_inclusive)
-        stop_excl.push_back('\0');
-
-    /* ---- fused single-launch fast path (small ranges, the YCSB-E shape):
-     * one pinned H2D of the request bytes, one launch, one pinned D2H of
-     * hdr + blob prefix, one sync ---- */
-    if (!e->runs.empty() && (int)e->runs.size() <= RRDB_MAX_RUNS) {
-        e->mg_lane_init();
-        MgFusedArgs fa{};
-        uint64_t in_n = start.size() + stop_excl.size() + q->sort_key_filter_pattern.len;
-        const uint8_t *d_blob = nullptr;
-        const uint8_t *h_resp = e->mg_hout;
-        bool served = false;
-        int32_t fused_lane = RRDB_MG_LANE_SMALL;
-        if (sizeof(MgGraphHdr) + in_n <= MG_GRAPH_IN && e->mg_persist_wanted() &&
-            e->server_ready()) {
-            /* resident-kernel lane: write the request slice, bump the
-             * doorbell, spin for completion */
-            MgGraphHdr *hh = (MgGraphHdr *)e->mg_mb->req;
-            hh->start_len = (uint32_t)start.size();
-            hh->stop_len = (uint32_t)stop_excl.size();
-            hh->sk_pat_len = (uint32_t)q->sort_key_filter_pattern.len;
-            hh->start_inclusive = start_inclusive;
-            hh->stop_inclusive = stop_inclusive;
-            hh->reverse = q->reverse;
-            hh->no_value = q->no_value;
-            hh->max_kv_count = max_kv_count;
-            hh->max_iteration_count = max_iteration_count;
-            hh->max_iteration_size = max_iter_size;
-            hh->sk_ft = q->sort_key_filter_type;
-            hh->epoch_now = epoch_now;
-            hh->data_version = e->data_version;
-            hh->hash_key_skip = 2 + q->hash_key.len;
-            uint8_t *pp = e->mg_mb->req + sizeof(MgGraphHdr);
-            memcpy(pp, start.data(), start.size());
-            pp += start.size();
-            memcpy(pp, stop_excl.data(), stop_excl.size());
-            pp += stop_excl.size();
-            if (q->sort_key_filter_pattern.len)
-                memcpy(pp, q->sort_key_filter_pattern.data, q->sort_key_filter_pattern.len);
-            uint64_t seq = ++e->mg_srv_seq;
-            __atomic_store_n(&e->mg_mb->req_seq, seq, __ATOMIC_RELEASE);
-            auto t0 = std::chrono::steady_clock::now();
-            bool ok = true;
-            while (__atomic_load_n(&e->mg_mb->done_seq, __ATOMIC_ACQUIRE) != seq) {
-                auto ms = std::chrono::duration_cast<std::chrono::milliseconds>(
-                              std::chrono::steady_clock::now() - t0)
-                              .count();
-                if (ms > 2 && !__atomic_load_n(&e->mg_mb->alive, __ATOMIC_ACQUIRE)) {
-                    /* idle-expired between the readiness check and the
-                     * doorbell: relaunch (seq rewound so the fresh kernel
-                     * sees this request as new) and re-ring */
-                    e->mg_srv_gen = ~0ull;
-                    e->mg_srv_seq = seq - 1;
-                    bool up = e->server_ready();
-                    e->mg_srv_seq = seq;
-                    if (!up) {
-                        ok = false;
-                        break;
-                    }
-                    __atomic_store_n(&e->mg_mb->req_seq, seq, __ATOMIC_RELEASE);
-                    t0 = std::chrono::steady_clock::now();
-                    continue;
-                }
-                if (ms > 200) {
-                    ok = false; /* server died: fall to the graph lane */
+/* ---- fused single-launch fast path (small ranges, the YCSB-E shape), at most
+ * RRDB_MAX_RUNS runs: one pinned H2D of the request bytes, one launch, one
+ * pinned D2H of hdr + blob prefix, one sync; or the same kernel body behind the
+ * resident server or the captured graph.  False: range too large or a row
+ * oversize, the general lane has to serve it. ---- */
+static bool mg_fused(HipEngine *e, const rrdb_multi_get_request *q, const KeyRange &kr,
+                     const MgLimits &lim, uint32_t epoch_now, rrdb_result *out, Arena *a,
+                     rrdb_multi_get_lane *rep)
+{
+    const std::string &start = kr.start, &stop_excl = kr.stop_excl;
+    e->mg_lane_init();
+    MgFusedArgs fa{};
+    uint64_t in_n = start.size() + stop_excl.size() + q->sort_key_filter_pattern.len;
+    const uint8_t *d_blob = nullptr;
+    const uint8_t *h_resp = e->mg_hout;
+    bool served = false;
+    int32_t fused_lane = RRDB_MG_LANE_SMALL;
+    /* the request slice of the server and graph lanes: MgGraphHdr, then the bytes */
+    auto fill_slice = [&](uint8_t *req) {
+        MgGraphHdr *hh = (MgGraphHdr *)req;
+        hh->start_len = (uint32_t)start.size();
+        hh->stop_len = (uint32_t)stop_excl.size();
+        hh->sk_pat_len = (uint32_t)q->sort_key_filter_pattern.len;
+        hh->start_inclusive = kr.start_inclusive;
+        hh->stop_inclusive = kr.stop_inclusive;
+        hh->reverse = q->reverse;
+        hh->no_value = q->no_value;
+        hh->max_kv_count = lim.max_kv_count;
+        hh->max_iteration_count = lim.max_iteration_count;
+        hh->max_iteration_size = lim.max_iter_size;
+        hh->sk_ft = q->sort_key_filter_type;
+        hh->epoch_now = epoch_now;
+        hh->data_version = e->data_version;
+        hh->hash_key_skip = 2 + q->hash_key.len;
+        uint8_t *pp = req + sizeof(MgGraphHdr);
+        memcpy(pp, start.data(), start.size());
+        pp += start.size();
+        memcpy(pp, stop_excl.data(), stop_excl.size());
+        pp += stop_excl.size();
+        if (q->sort_key_filter_pattern.len)
+            memcpy(pp, q->sort_key_filter_pattern.data, q->sort_key_filter_pattern.len);
+    };
+    if (sizeof(MgGraphHdr) + in_n <= MG_GRAPH_IN && e->mg_persist_wanted() &&
+        e->server_ready()) {
+        /* resident-kernel lane: write the request slice, bump the doorbell, spin for completion */
+        fill_slice(e->mg_mb->req);
+        uint64_t seq = ++e->mg_srv_seq;
+        __atomic_store_n(&e->mg_mb->req_seq, seq, __ATOMIC_RELEASE);
+        auto t0 = std::chrono::steady_clock::now();
+        bool ok = true;
+        while (__atomic_load_n(&e->mg_mb->done_seq, __ATOMIC_ACQUIRE) != seq) {
+            auto ms = std::chrono::duration_cast<std::chrono::milliseconds>(
+                          std::chrono::steady_clock::now() - t0)
+                          .count();
+            if (ms > 2 && !__atomic_load_n(&e->mg_mb->alive, __ATOMIC_ACQUIRE)) {
+                /* idle-expired between the readiness check and the doorbell: relaunch (seq
+                 * rewound so the fresh kernel sees this request as new) and re-ring */
+                e->mg_srv_gen = ~0ull;
+                e->mg_srv_seq = seq - 1;
+                bool up = e->server_ready();
+                e->mg_srv_seq = seq;
+                if (!up) {
+                    ok = false;
                     break;
                 }
+                __atomic_store_n(&e->mg_mb->req_seq, seq, __ATOMIC_RELEASE);
+                t0 = std::chrono::steady_clock::now();
+                continue;
             }
-            if (ok) {
-                h_resp = e->mg_mb->resp;
-                d_blob = e->mg_dout + 32;
-                served = true;
-                fused_lane = RRDB_MG_LANE_SERVER;
+            if (ms > 200) {
+                ok = false; /* server died: fall to the graph lane */
+                break;
             }
         }
-        if (!served && sizeof(MgGraphHdr) + in_n <= MG_GRAPH_IN && e->mg_graph_ready()) {
-            /* captured-graph lane: fill the request slice, one graph launch */
-            MgGraphHdr *hh = (MgGraphHdr *)e->mg_hin;
-            hh->start_len = (uint32_t)start.size();
-            hh->stop_len = (uint32_t)stop_excl.size();
-            hh->sk_pat_len = (uint32_t)q->sort_key_filter_pattern.len;
-            hh->start_inclusive = start_inclusive;
-            hh->stop_inclusive = stop_inclusive;
-            hh->reverse = q->reverse;
-            hh->no_value = q->no_value;
-            hh->max_kv_count = max_kv_count;
-            hh->max_iteration_count = max_iteration_count;
-            hh->max_iteration_size = max_iter_size;
-            hh->sk_ft = q->sort_key_filter_type;
-            hh->epoch_now = epoch_now;
-            hh->data_version = e->data_version;
-            hh->hash_key_skip = 2 + q->hash_key.len;
-            uint8_t *pp = e->mg_hin + sizeof(MgGraphHdr);
-            memcpy(pp, start.data(), start.size());
-            pp += start.size();
-            memcpy(pp, stop_excl.data(), stop_excl.size());
-            pp += stop_excl.size();
-            if (q->sort_key_filter_pattern.len)
-                memcpy(pp, q->sort_key_filter_pattern.data, q->sort_key_filter_pattern.len);
-            HIP_OK(hipGraphLaunch(e->mg_graph, e->stream));
-            spin_sync(e->stream);
+        if (ok) {
+            h_resp = e->mg_mb->resp;
             d_blob = e->mg_dout + 32;
             served = true;
-            fused_lane = RRDB_MG_LANE_GRAPH;
+            fused_lane = RRDB_MG_LANE_SERVER;
         }
-        if (!served && in_n <= HipEngine::MG_IN_CAP) {
-            uint64_t o = 0;
-            memcpy(e->mg_hin + o, start.data(), start.size());
-            fa.start = e->mg_din + o;
-            o += start.size();
-            memcpy(e->mg_hin + o, stop_excl.data(), stop_excl.size());
-            fa.stop = e->mg_din + o;
-            o += stop_excl.size();
-            if (q->sort_key_filter_pattern.len)
-                memcpy(e->mg_hin + o, q->sort_key_filter_pattern.data,
-                       q->sort_key_filter_pattern.len);
-            fa.sk_pat = e->mg_din + o;
-            HIP_OK(hipMemcpyAsync(e->mg_din, e->mg_hin, in_n ? in_n : 1,
-                                  hipMemcpyHostToDevice, e->stream));
-        } else if (!served) { /* giant keys: pageable per-piece uploads */
-            fa.start = e->upload_tmp(start.data(), start.size());
-            fa.stop = e->upload_tmp(stop_excl.data(), stop_excl.size());
-            fa.sk_pat = e->upload_tmp(q->sort_key_filter_pattern.data,
-                                      q->sort_key_filter_pattern.len);
-        }
-        fa.start_len = start.size();
-        fa.stop_len = stop_excl.size();
-        fa.start_inclusive = start_inclusive;
-        fa.stop_inclusive = stop_inclusive;
-        fa.reverse = q->reverse;
-        fa.no_value = q->no_value;
-        fa.max_kv_count = max_kv_count;
-        fa.max_iteration_count = max_iteration_count;
-        fa.max_iteration_size = max_iter_size;
-        fa.sk_ft = q->sort_key_filter_type;
-        fa.sk_pat_len = q->sort_key_filter_pattern.len;
-        fa.epoch_now = epoch_now;
-        fa.data_version = e->data_version;
-        fa.hash_key_skip = 2 + q->hash_key.len;
-        if (!served) {
-            uint8_t *d_out = e->talloc<uint8_t>(32 + MG_BLOB_BYTES);
-            fa.out_hdr = (int64_t *)d_out;
-            fa.out_blob = d_out + 32;
-            launch_multi_get_small(e->dev_runs(), (int)e->runs.size(), fa, e->stream);
-            HIP_OK(hipMemcpyAsync(e->mg_hout, d_out, 32 + HipEngine::MG_OUT_PREFIX,
-                                  hipMemcpyDeviceToHost, e->stream));
-            spin_sync(e->stream);
-            d_blob = fa.out_blob;
-        }
-        const int64_t *hdr4 = (const int64_t *)h_resp;
-        if (hdr4[0] >= 0) {
-            rep->lane = fused_lane;
-            uint64_t m = (uint64_t)hdr4[0];
-            uint64_t kb = (uint64_t)hdr4[2], vb = (uint64_t)hdr4[3];
-            int64_t complete_flag = hdr4[1];
-            out->keys = (rrdb_slice *)a->alloc(m * sizeof(rrdb_slice));
-            out->values = (rrdb_slice *)a->alloc(m * sizeof(rrdb_slice));
-            if (m) {
-                uint64_t blob_n = 2 * (m + 1) * 8 + kb + vb;
-                uint8_t *hb = (uint8_t *)a->alloc(blob_n);
-                if (blob_n <= HipEngine::MG_OUT_PREFIX) {
-                    memcpy(hb, h_resp + 32, blob_n); /* already on host */
-                } else {
-                    rep->tail_read = 1;
-                    HIP_OK(hipMemcpyAsync(hb, d_blob, blob_n, hipMemcpyDeviceToHost,
-                                          e->stream));
-                    HIP_OK(hipStreamSynchronize(e->stream));
-                }
-                const uint64_t *koffs = (const uint64_t *)hb;
-                const uint64_t *voffs = koffs + (m + 1);
-                uint8_t *hk = hb + 2 * (m + 1) * 8;
-                uint8_t *hv = hk + kb;
-                for (uint64_t j = 0; j < m; j++) {
-                    out->keys[j] = {hk + koffs[j], koffs[j + 1] - koffs[j]};
-                    out->values[j] = {hv + voffs[j], voffs[j + 1] - voffs[j]};
-                }
-            }
-            out->count = m;
-            out->error = complete_flag ? RRDB_OK : RRDB_INCOMPLETE;
-            return out->error;
-        }
-        /* fallback: large range or oversize rows — general path below */
-        rep->fused_first = fused_lane;
     }
+    if (!served && sizeof(MgGraphHdr) + in_n <= MG_GRAPH_IN && e->mg_graph_ready()) {
+        /* captured-graph lane: fill the request slice, one graph launch */
+        fill_slice(e->mg_hin);
+        HIP_OK(hipGraphLaunch(e->mg_graph, e->stream));
+        spin_sync(e->stream);
+        d_blob = e->mg_dout + 32;
+        served = true;
+        fused_lane = RRDB_MG_LANE_GRAPH;
+    }
+    if (!served && in_n <= HipEngine::MG_IN_CAP) {
+        uint64_t o = 0;
+        memcpy(e->mg_hin + o, start.data(), start.size());
+        fa.start = e->mg_din + o;
+        o += start.size();
+        memcpy(e->mg_hin + o, stop_excl.data(), stop_excl.size());
+        fa.stop = e->mg_din + o;
+        o += stop_excl.size();
+        if (q->sort_key_filter_pattern.len)
+            memcpy(e->mg_hin + o, q->sort_key_filter_pattern.data, q->sort_key_filter_pattern.len);
+        fa.sk_pat = e->mg_din + o;
+        HIP_OK(hipMemcpyAsync(e->mg_din, e->mg_hin, in_n ? in_n : 1,
+                              hipMemcpyHostToDevice, e->stream));
+    } else if (!served) { /* giant keys: pageable per-piece uploads */
+        fa.start = e->upload_tmp(start.data(), start.size());
+        fa.stop = e->upload_tmp(stop_excl.data(), stop_excl.size());
+        fa.sk_pat = e->upload_tmp(q->sort_key_filter_pattern.data, q->sort_key_filter_pattern.len);
+    }
+    fa.start_len = start.size();
+    fa.stop_len = stop_excl.size();
+    fa.start_inclusive = kr.start_inclusive;
+    fa.stop_inclusive = kr.stop_inclusive;
+    fa.reverse = q->reverse;
+    fa.no_value = q->no_value;
+    fa.max_kv_count = lim.max_kv_count;
+    fa.max_iteration_count = lim.max_iteration_count;
+    fa.max_iteration_size = lim.max_iter_size;
+    fa.sk_ft = q->sort_key_filter_type;
+    fa.sk_pat_len = q->sort_key_filter_pattern.len;
+    fa.epoch_now = epoch_now;
+    fa.data_version = e->data_version;
+    fa.hash_key_skip = 2 + q->hash_key.len;
+    if (!served) {
+        uint8_t *d_out = e->talloc<uint8_t>(32 + MG_BLOB_BYTES);
+        fa.out_hdr = (int64_t *)d_out;
+        fa.out_blob = d_out + 32;
+        launch_multi_get_small(e->dev_runs(), (int)e->runs.size(), fa, e->stream);
+        HIP_OK(hipMemcpyAsync(e->mg_hout, d_out, 32 + HipEngine::MG_OUT_PREFIX,
+                              hipMemcpyDeviceToHost, e->stream));
+        spin_sync(e->stream);
+        d_blob = fa.out_blob;
+    }
+    const int64_t *hdr4 = (const int64_t *)h_resp;
+    if (hdr4[0] >= 0) {
+        rep->lane = fused_lane;
+        uint64_t m = (uint64_t)hdr4[0];
+        uint64_t kb = (uint64_t)hdr4[2], vb = (uint64_t)hdr4[3];
+        int64_t complete_flag = hdr4[1];
+        out->keys = (rrdb_slice *)a->alloc(m * sizeof(rrdb_slice));
+        out->values = (rrdb_slice *)a->alloc(m * sizeof(rrdb_slice));
+        if (m) {
+            uint64_t blob_n = 2 * (m + 1) * 8 + kb + vb;
+            uint8_t *hb = (uint8_t *)a->alloc(blob_n);
+            if (blob_n <= HipEngine::MG_OUT_PREFIX) {
+                memcpy(hb, h_resp + 32, blob_n); /* already on host */
+            } else {
+                rep->tail_read = 1;
+                HIP_OK(hipMemcpyAsync(hb, d_blob, blob_n, hipMemcpyDeviceToHost, e->stream));
+                HIP_OK(hipStreamSynchronize(e->stream));
+            }
+            const uint64_t *koffs = (const uint64_t *)hb;
+            const uint64_t *voffs = koffs + (m + 1);
+            uint8_t *hk = hb + 2 * (m + 1) * 8;
+            uint8_t *hv = hk + kb;
+            for (uint64_t j = 0; j < m; j++) {
+                out->keys[j] = {hk + koffs[j], koffs[j + 1] - koffs[j]};
+                out->values[j] = {hv + voffs[j], voffs[j + 1] - voffs[j]};
+            }
+        }
+        out->count = m;
+        out->error = complete_flag ? RRDB_OK : RRDB_INCOMPLETE;
+        return true;
+    }
+    /* fallback: large range or oversize rows — the general lane */
+    rep->fused_first = fused_lane;
+    return false;
+}
 
-    rep->lane = RRDB_MG_LANE_GENERAL;
-    uint64_t *d_view = nullptr, n = 0;
-    e->build_view(&start, &stop_excl, &d_view, &n);
+/* the general lane: the range's view, the per-record state of a window of it,
+ * and the reference's limiter loop over that window on the host */
+static int32_t mg_general(HipEngine *e, const rrdb_multi_get_request *q, const KeyRange &kr,
+                          const MgLimits &lim, uint32_t epoch_now, rrdb_result *out, Arena *a)
+{
+    const std::string &start = kr.start, &stop = kr.stop;
+    const bool start_inclusive = kr.start_inclusive, stop_inclusive = kr.stop_inclusive;
+    const DevView view = e->build_view(&start, &kr.stop_excl);
+    const uint64_t *d_view = view.d;
+    const uint64_t n = view.n;
     if (n == 0) {
-        if (d_view)
-            (void)hipFree(d_view);
         out->error = RRDB_OK;
         return RRDB_OK;
     }
     /* window: the limiter consumes at most mg_max_iter_count iterations plus
      * one possible uncounted first/last-exclusive skip */
-    uint64_t wcap = (uint64_t)max_iteration_count + 1;
+    uint64_t wcap = (uint64_t)lim.max_iteration_count + 1;
     uint64_t wstart = 0, w = std::min<uint64_t>(n, wcap);
     if (q->reverse)
         wstart = n - w;
     DevRun *dr = e->dev_runs();
-    ScanParams sp{};
-    sp.epoch_now = epoch_now;
-    sp.data_version = e->data_version;
-    sp.pidx = e->pidx;
-    sp.partition_version = e->partition_version;
-    sp.validate_hash = 0; /* multi_get does no hash validation */
-    sp.hk_ft = 0;
+    /* no hash validation, no hash-key filter */
+    ScanParams sp = base_scan_params(e, epoch_now);
     sp.sk_ft = q->sort_key_filter_type;
-    sp.sk_pat = nullptr;
     sp.sk_pat_len = q->sort_key_filter_pattern.len;
     uint8_t *d_skpat = e->upload_tmp(q->sort_key_filter_pattern.data, sp.sk_pat_len);
     sp.sk_pat = d_skpat;
@@ -2871,44 +2867,23 @@ static int32_t multi_get_locked(void *h, const rrdb_multi_get_request *q, uint32
      * reverse walk (on_multi_get:697-700) — excluded, and it keeps the
      * iterator Valid() on a limit exit */
     uint64_t lo_skip = 0;
-    if (q->reverse && !start_inclusive && wstart == 0 && n > 0) {
-        uint32_t *d_eq = e->talloc<uint32_t>(4);
-        uint8_t *d_b = e->upload_tmp(start.data(), start.size());
-        launch_first_eq(dr, d_view, 1, d_b, start.size(), d_eq, e->stream);
-        uint32_t eq = 0;
-        HIP_OK(hipMemcpyAsync(&eq, d_eq, 4, hipMemcpyDeviceToHost, e->stream));
-        HIP_OK(hipStreamSynchronize(e->stream));
-        e->tfree(d_eq);
-        e->tfree(d_b);
-        lo_skip = eq ? 1 : 0;
-    }
+    if (q->reverse && !start_inclusive && wstart == 0 && n > 0)
+        lo_skip = key_at_equals(e, d_view, start) ? 1 : 0;
     uint64_t steps = w;
     for (uint64_t s = 0; s < steps; s++) {
         uint64_t wi = q->reverse ? (steps - 1 - s) : s;
         if (q->reverse && lo_skip && wi == 0)
             break; /* reached the excluded == start record: out of range */
-        if (count >= (int64_t)max_kv_count || iteration_count >= max_iteration_count ||
-            size >= max_iter_size)
+        if (count >= (int64_t)lim.max_kv_count || iteration_count >= lim.max_iteration_count ||
+            size >= lim.max_iter_size)
             break;
-        /* first-exclusive skip of the exact boundary key */
+        /* first-exclusive skip of the exact boundary key: the host has the
+         * sizes only, so a device compare */
         if (s == 0) {
-            /* check boundary equality via sizes: need the key — use a cheap
-             * device compare */
             bool check = (!q->reverse && !start_inclusive) || (q->reverse && !stop_inclusive);
-            if (check) {
-                const std::string &bound = q->reverse ? stop : start;
-                uint32_t *d_eq = e->talloc<uint32_t>(4);
-                uint8_t *d_b = e->upload_tmp(bound.data(), bound.size());
-                launch_first_eq(dr, d_view + wstart + wi, 1, d_b, bound.size(), d_eq, e->stream);
-                uint32_t eq = 0;
-                HIP_OK(hipMemcpyAsync(&eq, d_eq, 4, hipMemcpyDeviceToHost, e->stream));
-                HIP_OK(hipStreamSynchronize(e->stream));
-                e->tfree(d_eq);
-                e->tfree(d_b);
-                if (eq) {
-                    skipped_first = true;
-                    continue;
-                }
+            if (check && key_at_equals(e, d_view + wstart + wi, q->reverse ? stop : start)) {
+                skipped_first = true;
+                continue;
             }
         }
         iteration_count++;
@@ -2930,20 +2905,11 @@ static int32_t multi_get_locked(void *h, const rrdb_multi_get_request *q, uint32
             ((!q->reverse && stop_inclusive) || (q->reverse && start_inclusive))) {
             /* last iterated in-range record = the far end of the view */
             uint64_t vidx = q->reverse ? (lo_skip) : (n - 1);
-            const std::string &bnd = q->reverse ? start : stop;
-            uint32_t *d_eq = e->talloc<uint32_t>(4);
-            uint8_t *d_b = e->upload_tmp(bnd.data(), bnd.size());
-            launch_first_eq(dr, d_view + vidx, 1, d_b, bnd.size(), d_eq, e->stream);
-            uint32_t eq = 0;
-            HIP_OK(hipMemcpyAsync(&eq, d_eq, 4, hipMemcpyDeviceToHost, e->stream));
-            HIP_OK(hipStreamSynchronize(e->stream));
-            e->tfree(d_eq);
-            e->tfree(d_b);
-            boundary_hit = eq != 0;
+            boundary_hit = key_at_equals(e, d_view + vidx, q->reverse ? start : stop);
         }
-        bool limit_exit = !boundary_hit &&
-                          (count >= (int64_t)max_kv_count ||
-                           iteration_count >= max_iteration_count || size >= max_iter_size);
+        bool limit_exit = !boundary_hit && (count >= (int64_t)lim.max_kv_count ||
+                                            iteration_count >= lim.max_iteration_count ||
+                                            size >= lim.max_iter_size);
         uint64_t countable = w - (skipped_first ? 1 : 0) - lo_skip;
         bool consumed_all = (iteration_count >= countable);
         if (w < n || !consumed_all)
@@ -2953,7 +2919,7 @@ static int32_t multi_get_locked(void *h, const rrdb_multi_get_request *q, uint32
         else if (q->reverse)
             complete = !(lo_skip || valid_beyond(e, start, true));
         else
-            complete = !valid_beyond(e, stop_excl, false);
+            complete = !valid_beyond(e, kr.stop_excl, false);
     }
     uint64_t m = sel.size();
     if (q->reverse)
@@ -2994,10 +2960,45 @@ static int32_t multi_get_locked(void *h, const rrdb_multi_get_request *q, uint32
         e->tfree(d_vout);
     }
     e->tfree(d_skpat);
-    (void)hipFree(d_view);
     out->count = m;
     out->error = complete ? RRDB_OK : RRDB_INCOMPLETE; /* :789-799 */
     return out->error;
+}
+
+/* body of on_multi_get; caller holds the engine lock */
+static int32_t multi_get_locked(void *h, const rrdb_multi_get_request *q, uint32_t epoch_now,
+                                rrdb_result *out, rrdb_multi_get_lane *rep)
+{
+    auto *e = (HipEngine *)h;
+    /* a batch's per-request fallbacks hand in a scratch report */
+    rep->lane = RRDB_MG_LANE_NONE;
+    rep->fused_first = RRDB_MG_LANE_NONE;
+    rep->tail_read = 0;
+    Arena *a = read_begin(e, out);
+    if (!a)
+        return out->error;
+    e->activate();
+    if (q->sort_key_filter_type < 0 || q->sort_key_filter_type > 3 ||
+        !hklen_ok(q->hash_key.len)) {
+        out->error = RRDB_INVALID_ARGUMENT; /* on_multi_get:508-517 */
+        return out->error;
+    }
+    const MgLimits lim(e, q);
+    if (q->n_sort_keys > 0) {
+        rep->lane = RRDB_MG_LANE_POINT_LIST;
+        return mg_point_list(e, q, lim, epoch_now, out, a);
+    }
+    /* range variant (on_multi_get:540-778) */
+    KeyRange kr = mg_range(q);
+    if (!kr.close()) {
+        out->error = RRDB_OK; /* empty range: no lane */
+        return RRDB_OK;
+    }
+    if (!e->runs.empty() && (int)e->runs.size() <= RRDB_MAX_RUNS &&
+        mg_fused(e, q, kr, lim, epoch_now, out, a, rep))
+        return out->error;
+    rep->lane = RRDB_MG_LANE_GENERAL;
+    return mg_general(e, q, kr, lim, epoch_now, out, a);
 }
 
 int32_t rrdb_multi_get(void *h, const rrdb_multi_get_request *q, uint32_t epoch_now,
@@ -5173,19 +5174,15 @@ extern "C" int32_t rrdb_multi_get_batch(void *h, uint64_t n_req, const uint8_t *
     std::vector<uint64_t> used(n_req, 0), pack_off(n_req + 1, 0);
     std::vector<uint8_t> packed_host;
     if (fused_ok && n_req > 0) {
-        uint32_t max_kv_count = e->mg_max_iter_count;
-        if (shared->max_kv_count > 0 && (uint32_t)shared->max_kv_count < max_kv_count)
-            max_kv_count = (uint32_t)shared->max_kv_count;
-        int64_t max_kv_size = shared->max_kv_size > 0 ? shared->max_kv_size : INT32_MAX;
+        const MgLimits lim(e, shared);
         MgFusedArgs fa{};
         fa.start_inclusive = 1;
         fa.stop_inclusive = 0;
         fa.reverse = shared->reverse;
         fa.no_value = shared->no_value;
-        fa.max_kv_count = max_kv_count;
-        fa.max_iteration_count = e->mg_max_iter_count;
-        fa.max_iteration_size = std::min<int64_t>(
-            max_kv_size, e->mg_max_iter_size > 0 ? (int64_t)e->mg_max_iter_size : INT32_MAX);
+        fa.max_kv_count = lim.max_kv_count;
+        fa.max_iteration_count = lim.max_iteration_count;
+        fa.max_iteration_size = lim.max_iter_size;
         fa.sk_ft = shared->sort_key_filter_type;
         fa.sk_pat_len = shared->sort_key_filter_pattern.len;
         fa.sk_pat = e->upload_tmp(shared->sort_key_filter_pattern.data, fa.sk_pat_len);

@@ -423,6 +423,59 @@ RC_MULTI_GETS = {
 }
 RC_SCAN = dict(start_key=b"\x00\x00", stop_key=b"\xff\xff", batch_size=3)
 
+# ---- the sort-key prefix filter's clamp of both ends of the range ----
+# A prefix filter narrows [start, stop) to the keys that carry the prefix
+# before any lane sees the range (on_multi_get:558-578).  The filter itself
+# hides what a missing clamp lets in, so rows alone do not show it: the
+# iteration cap does.  The walk over a clamped range ends at the prefix's last
+# key; over an unclamped one it goes on into the filtered keys behind it
+# (forward), or starts among them (reverse), and runs into the cap.
+PFX = b"p"
+PFX_HK, PFX_HK_WIDE = b"pfx", b"pfx-wide"  # the second holds a row over ROW_MAX: general lane
+PFX_BEFORE = [b"a%d" % i for i in range(4)]
+PFX_IN = [b"p"] + [b"p%d" % i for i in range(9)] + [b"p\xff"]  # b"p" is the clamped start itself
+PFX_AFTER = [b"q"] + [b"q%d" % i for i in range(4)] + [b"z"]    # b"q" is the clamped stop itself
+PFX_ITERATED = len(PFX_IN) - 1          # p1's newest version is a tombstone
+PFX_ITER_CAP = PFX_ITERATED + 2         # the clamped walk fits; two keys further does not
+
+
+def pfx_runs():
+    """two runs with overlapping keys: run 0 puts every sortkey of both
+    hashkeys, run 1 lays newer puts over both bounds and tombstones, an
+    expired and a live TTL over keys inside and outside the prefix"""
+    run0, run1 = {}, {}
+    for hk in (PFX_HK, PFX_HK_WIDE):
+        for sk in PFX_BEFORE + PFX_IN + PFX_AFTER:
+            run0[D.generate_key(hk, sk)] = (D.encode_value(b"old-" + sk, 0, 0, 1), 0)
+        wide = body_bytes(hk, 8, ROW_MAX + 1) if hk == PFX_HK_WIDE else b"narrow"
+        newer = {b"p": b"new-p", b"q": b"new-q", b"a1": b"new-a1", b"p8": wide}
+        for sk, body in newer.items():
+            run1[D.generate_key(hk, sk)] = (D.encode_value(body, 0, 0, 1), 0)
+        for sk in (b"p1", b"q1"):
+            run1[D.generate_key(hk, sk)] = (b"", 1)
+        run1[D.generate_key(hk, b"p2")] = (D.encode_value(b"dead", 500, 0, 1), 0)
+        run1[D.generate_key(hk, b"p3")] = (D.encode_value(b"ttl", NOW + 100, 0, 1), 0)
+    return [[(k, recs[k][0], r * 1000 + i + 1, recs[k][1]) for i, k in enumerate(sorted(recs))]
+            for r, recs in enumerate((run0, run1))]
+
+
+def _pfx_cases():
+    """a bound exactly on an existing key at each end, forward and reverse.
+    whole_hashkey and its reverse are the ones that tell a missing stop clamp:
+    the other shapes' own stop keys end the walk inside PFX_ITER_CAP anyway."""
+    shapes = {
+        "whole_hashkey": {},
+        "start_on_bound_excl": dict(start_sortkey=b"p", start_inclusive=False),
+        "stop_on_bound_incl": dict(stop_sortkey=b"q", stop_inclusive=True),
+        "around": dict(start_sortkey=b"a2", stop_sortkey=b"q2", stop_inclusive=True),
+    }
+    flt = dict(sort_key_filter_type=FT_MATCH_PREFIX, sort_key_filter_pattern=PFX)
+    return {name + ("-rev" if rev else ""): dict(kw, reverse=rev, **flt)
+            for name, kw in shapes.items() for rev in (False, True)}
+
+
+PFX_CASES = _pfx_cases()
+
 # ---- scans (the device-resident output is read back on these) ----
 SCAN_CASES = [dict(start_key=D.generate_key(b"u000"), stop_key=D.generate_key(b"u060"),
                    batch_size=bs, no_value=nv)

@@ -26,7 +26,8 @@ from incubator_pegasus_amd.capi import (MG_LANE_GENERAL, MG_LANE_NONE, OK,
                                         ROUTE_RANK_GRP, ROUTE_RANK_LDS, SCAN_COMPLETED,
                                         _MultiGetRequest, _Result, _ScanRequest, _cslice, _pack)
 from mg_lane_cases import NOW
-from test_mg_lanes_model import rc_reads
+from pymodel import Model
+from test_mg_lanes_model import ITER_COUNT_ENV, rc_reads
 from test_scan_differential import _drain_batches
 
 pytestmark = pytest.mark.gpu
@@ -92,6 +93,39 @@ def test_server_buffer_across_tail_reads(trio, want_single):
             c = by[name]
             assert g.multi_get(c.hk, NOW, **c.kw) == want_single[name], (rep, name)
             assert _lane(g) == MC.expected_lane(c, "server"), (rep, name)
+
+
+@pytest.mark.parametrize("setting", sorted(MC.LANE_SETTINGS))
+def test_prefix_clamp_cases(oracle_lib, hip_lib, setting):
+    """A sort-key prefix filter clamps both ends of the range before a lane
+    sees it.  Two overlapping runs, no compaction, an iteration cap that the
+    clamped walk just fits: engine == oracle == model on every case, on a
+    fused lane and, for the hashkey with the over-long row, on the general one."""
+    o = oracle_lib.open(1, 0, -1)
+    g = hip_lib.open(1, 0, 0)
+    try:
+        m = Model()
+        for r in MC.pfx_runs():
+            o.ingest_run(r)
+            g.ingest_run(r)
+            m.ingest(r)
+        g.set_envs(MC.LANE_SETTINGS[setting])
+        fused = MC.FUSED_LANE[setting]
+        for cap in (MC.PFX_ITER_CAP, MC.MG_ITER_COUNT):
+            o.set_envs({ITER_COUNT_ENV: str(cap)})
+            g.set_envs({ITER_COUNT_ENV: str(cap)})
+            for hk, lane in ((MC.PFX_HK, (fused, MG_LANE_NONE, 0)),
+                             (MC.PFX_HK_WIDE, (MG_LANE_GENERAL, fused, 0))):
+                for name, kw in MC.PFX_CASES.items():
+                    want = m.multi_get(hk, NOW, engine_max_iter=cap, **kw)
+                    assert want[0] == OK and len(want[1]) >= MC.PFX_ITERATED - 2
+                    assert o.multi_get(hk, NOW, **kw) == want, (cap, hk, name)
+                    assert g.multi_get(hk, NOW, **kw) == want, (cap, hk, name)
+                    assert _lane(g) == lane, (cap, hk, name)
+        assert g.num_runs() == 2
+    finally:
+        o.close()
+        g.close()
 
 
 # ---------------- batch ----------------

@@ -123,6 +123,45 @@ def test_run_count_handles_oracle_vs_model(oracle_lib, shape, n_runs):
         o.close()
 
 
+ITER_COUNT_ENV = "rocksdb.multi_get_max_iteration_count"
+
+
+def test_prefix_clamp_oracle_vs_model(oracle_lib):
+    """the prefix-clamp cases: the oracle against the model, and the cases
+    are what they claim: under PFX_ITER_CAP a walk over the clamped range
+    completes with every row of the prefix, keys lie behind the prefix for a
+    longer walk to run into, and the cap is tight enough to tell"""
+    runs = MC.pfx_runs()
+    assert len(runs) == 2 and all(len(r) <= 200 for r in runs)
+    assert {k for k, _, _, _ in runs[0]} > {k for k, _, _, _ in runs[1]}  # overlapping keys
+    o = oracle_lib.open(1, 0, -1)
+    try:
+        m = Model()
+        for r in runs:
+            o.ingest_run(r)
+            m.ingest(r)
+        for hk in (MC.PFX_HK, MC.PFX_HK_WIDE):
+            rows = m.multi_get(hk, NOW, **MC.PFX_CASES["whole_hashkey"])[1]
+            assert len(rows) == MC.PFX_ITERATED - 1  # all but the expired one
+            assert rows[0][0] == MC.PFX and rows[-1][0] == MC.PFX_IN[-1]
+            assert len(m.multi_get(hk, NOW, start_sortkey=b"q")[1]) > 2  # behind the prefix
+            for cap in (MC.PFX_ITER_CAP, MC.MG_ITER_COUNT):
+                o.set_envs({ITER_COUNT_ENV: str(cap)})
+                for name, kw in MC.PFX_CASES.items():
+                    want = m.multi_get(hk, NOW, engine_max_iter=cap, **kw)
+                    assert o.multi_get(hk, NOW, **kw) == want, (hk, cap, name)
+                    excl = name.startswith("start_on_bound_excl")
+                    assert want == (OK, rows[1:] if excl else rows), (hk, cap, name)
+            # the cap is what tells: one short of it, the walk no longer fits
+            short = m.multi_get(hk, NOW, engine_max_iter=MC.PFX_ITERATED - 1,
+                                **MC.PFX_CASES["whole_hashkey"])
+            assert short[0] == INCOMPLETE
+        wide = m.multi_get(MC.PFX_HK_WIDE, NOW, **MC.PFX_CASES["whole_hashkey"])[1]
+        assert max(len(v) for _, v in wide) == MC.ROW_MAX + 1
+    finally:
+        o.close()
+
+
 # ---------------- the cases are what their names say ----------------
 
 def test_cases_are_what_they_claim(data):
