@@ -541,6 +541,48 @@ struct DevView {
     ~DevView() { if (d) (void)hipFree(d); }
 };
 
+/* the phase events of one call; destroyed on every way out of it */
+template <int N> struct PhaseEvents {
+    hipEvent_t ev[N];
+    PhaseEvents()
+    {
+        for (auto &x : ev)
+            HIP_OK(hipEventCreate(&x));
+    }
+    PhaseEvents(const PhaseEvents &) = delete;
+    PhaseEvents &operator=(const PhaseEvents &) = delete;
+    ~PhaseEvents()
+    {
+        for (auto &x : ev)
+            (void)hipEventDestroy(x);
+    }
+    void record(int i, hipStream_t s) { HIP_OK(hipEventRecord(ev[i], s)); }
+    /* false (and *out untouched) when either event has not completed */
+    bool ms(int i, int j, float *out) const
+    {
+        return hipEventElapsedTime(out, ev[i], ev[j]) == hipSuccess;
+    }
+};
+
+/* an exclusive scan's grand total is its last entry plus the last input: both
+ * copies, into out[0] and out[1]; the caller adds them after its sync */
+static void scan_tail_async(const uint64_t *d_scan, const uint64_t *d_in, uint64_t n,
+                            uint64_t out[2], hipStream_t st)
+{
+    HIP_OK(hipMemcpyAsync(&out[0], d_scan + n - 1, 8, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(&out[1], d_in + n - 1, 8, hipMemcpyDeviceToHost, st));
+}
+
+/* group-streaming rank: records of the anchor run per group, as a shift.  A
+ * group stages about GRP_TARGET records over all R runs. */
+static int grp_shift(int R)
+{
+    int gs = 4;
+    while ((1ull << (gs + 1)) * (uint64_t)R <= GRP_TARGET && gs < 8)
+        gs++;
+    return gs;
+}
+
 struct HipScanCtx {
     int64_t id = 0;
     uint32_t parked_at = 0; /* epoch_now when (re-)parked; 5-min GC */
@@ -588,53 +630,73 @@ struct HipEngine {
     DevRun *d_runs = nullptr;
     bool d_runs_dirty = true;
     int ldst_elig_cache = -1; /* -1 unknown; recomputed when the run set changes */
-    /* phase-1 state of a split compaction (rrdb_manual_compact_begin):
-     * device pointers are arena memory, valid until the next scratch_reset */
-    struct PendingCompact {
+    /* ---- compaction: the pending pass and what outlives it ---- */
+    /* One pass, built by compact_begin and consumed by compact_finish
+     * (rrdb_manual_compact_begin / _finish split the two).  Device pointers
+     * are arena memory under arena_pin until finish; none points into d_runs,
+     * so a run appended between begin and finish cannot invalidate the plan. */
+    struct CompactPlan {
         bool active = false, trivial = false, keep_inputs = false;
         /* the pass merges runs [first, first+R); bottommost iff first == 0 */
-        bool bottommost = true;
         size_t first = 0;
         int R = 0;
         uint64_t total = 0;
+        bool bottommost = true;
+        /* the emit the arrays below were built for: engine.emit_mode as begin
+         * read it (chunked for a window), so that a set_envs between begin
+         * and finish cannot send them to another emit kernel */
+        int emit_mode = 2;
+        uint32_t fk = 0, fv = 0; /* all-fixed-stride emit (ksz/vsz/kpos skipped) */
+        bool no_rewrite = false;  /* changed/new_expire arrays skipped */
+        /* the window's DevRun rows, the pass's own copy: run ids in order[]
+         * index it */
         DevRun *dr = nullptr;
-        uint64_t *d_wp = nullptr, *d_order = nullptr, *d_keepw = nullptr;
+        uint64_t *d_lo = nullptr, *d_hi = nullptr, *d_wp = nullptr;
+        uint64_t *d_order = nullptr, *d_keepw = nullptr;
         uint8_t *d_changed = nullptr;
         uint32_t *d_new_expire = nullptr;
+        uint64_t *d_ksz = nullptr, *d_vsz = nullptr;
         uint64_t *d_kpos = nullptr, *d_koffs = nullptr, *d_voffs = nullptr;
         uint64_t *d_tile_base = nullptr; /* all-fixed-stride emit: first output row per tile */
         uint64_t *d_rank_of = nullptr;
-        CompactStatsDev *d_stats = nullptr;
-        uint32_t fk = 0, fv = 0; /* all-fixed-stride emit (ksz/vsz/kpos skipped) */
-        bool no_rewrite = false;  /* changed/new_expire arrays skipped */
-        /* the emit the arrays above were built for: engine.emit_mode as
-         * phase 1 read it (chunked for a window), so that a set_envs between
-         * begin and finish cannot send them to another emit kernel */
-        int emit_mode = 2;
-        hipEvent_t ev[6] = {};
+        CompactStatsDev *d_stats = nullptr; /* 8 banks, summed by finish */
         rrdb_compact_stats st{};
     } pend;
-    uint64_t *pend_sizes = nullptr; /* pinned [6]: output sizes d2h target */
-    CompactStatsDev *pend_stats_h = nullptr; /* pinned [8]: stats d2h target */
-    /* events of the last compaction pass, resolved lazily by phase_ms() so
-     * the keep_inputs finish can return without draining the emit */
-    hipEvent_t tev[6] = {};
-    bool tev_live = false, tev_have_emit = false;
+    /* what outlives a pass: the pinned read-back targets, its events (resolved
+     * lazily by phase_ms() so the keep_inputs finish can return without
+     * draining the emit) and the kernels it dispatched to
+     * (rrdb_last_compact_route: written in rank_pass / emit_pass only) */
+    struct CompactKept {
+        uint64_t *sizes = nullptr;        /* pinned [6]: output sizes d2h target */
+        CompactStatsDev *stats = nullptr; /* pinned [8]: stats d2h target */
+        hipEvent_t ev[6] = {};
+        bool ev_live = false, have_emit = false;
+        rrdb_compact_route route{RRDB_ROUTE_NONE, RRDB_ROUTE_NONE};
+        void init()
+        {
+            if (sizes)
+                return;
+            HIP_OK(hipHostMalloc((void **)&sizes, 6 * 8));
+            HIP_OK(hipHostMalloc((void **)&stats, 8 * sizeof(CompactStatsDev)));
+            for (auto &x : ev)
+                HIP_OK(hipEventCreate(&x));
+        }
+    } kept;
     void resolve_phase_events()
     {
-        if (!tev_live)
+        if (!kept.ev_live)
             return;
-        tev_live = false;
+        kept.ev_live = false;
         float ms;
-        HIP_OK(hipEventSynchronize(tev[1]));
-        HIP_OK(hipEventElapsedTime(&ms, tev[0], tev[1]));
+        HIP_OK(hipEventSynchronize(kept.ev[1]));
+        HIP_OK(hipEventElapsedTime(&ms, kept.ev[0], kept.ev[1]));
         phase_ms["compact_rank"] = ms;
         phase_ms["compact_flags"] = 0.0;
-        if (tev_have_emit) {
-            HIP_OK(hipEventSynchronize(tev[4]));
-            HIP_OK(hipEventElapsedTime(&ms, tev[3], tev[4]));
+        if (kept.have_emit) {
+            HIP_OK(hipEventSynchronize(kept.ev[4]));
+            HIP_OK(hipEventElapsedTime(&ms, kept.ev[3], kept.ev[4]));
             phase_ms["compact_emit"] = ms;
-            HIP_OK(hipEventElapsedTime(&ms, tev[0], tev[4]));
+            HIP_OK(hipEventElapsedTime(&ms, kept.ev[0], kept.ev[4]));
             phase_ms["compact_total"] = ms;
         }
     }
@@ -839,10 +901,6 @@ struct HipEngine {
                           0 = global searches + bound-table narrowing,
                           1 = LDS-staged full-key block rank
                           (env "engine.rank_mode": grp|ldst|global|lds) */
-    /* which kernels the last compaction pass dispatched to
-       (rrdb_last_compact_route): written at the branches of compact_begin /
-       compact_finish, read by nothing else */
-    rrdb_compact_route last_route{RRDB_ROUTE_NONE, RRDB_ROUTE_NONE};
     /* which lane the last rrdb_multi_get took and how the last
        rrdb_multi_get_batch split (rrdb_last_multi_get_lane): written at the
        branches of multi_get_locked / rrdb_multi_get_batch, read by nothing
@@ -904,11 +962,6 @@ struct HipEngine {
     bool window_word_eligible(size_t first, size_t n)
     {
         return (first == 0 && n == runs.size()) ? word_eligible() : word_eligible_range(first, n);
-    }
-    bool ldst_eligible() { return rank_mode == 3 && word_eligible(); }
-    bool grp_eligible()
-    {
-        return rank_mode == 4 && runs.size() <= LDST_MAXR && word_eligible();
     }
     bool ldst_eligible(size_t first, size_t n)
     {
@@ -1379,9 +1432,7 @@ struct HipEngine {
                 wmax = hi[r] - lo[r];
                 q0 = r;
             }
-        int gs = 4;
-        while ((1ull << (gs + 1)) * (uint64_t)R <= GRP_TARGET && gs < 8)
-            gs++;
+        const int gs = grp_shift(R);
         uint64_t n_groups = (wmax + (1ull << gs) - 1) >> gs;
         if (n_groups == 0)
             n_groups = 1;
@@ -1389,6 +1440,35 @@ struct HipEngine {
         launch_anchor_rows(dr, R, q0, d_lo, d_hi, gs, n_groups, d_anch, stream);
         *out_anch = d_anch;
         return n_groups;
+    }
+
+    /* The rank route of runs [first, first+R) and the tables its kernel narrows
+     * by: anchors for the group rank, else a one- or two-level bound table above
+     * bt_min_records.  Compaction and views each launch their own kernel. */
+    struct RankPrep {
+        int32_t route = RRDB_ROUTE_RANK_GLOBAL;
+        uint64_t *d_anch = nullptr, n_groups = 0;
+        uint64_t *d_bt_off = nullptr, *d_bt = nullptr;
+        int bound_levels = 0;
+    };
+    RankPrep prepare_rank(DevRun *dr, size_t first, int R, const std::vector<uint64_t> &lo,
+                          const std::vector<uint64_t> &hi, const uint64_t *d_lo,
+                          const uint64_t *d_hi, uint64_t total, uint64_t bt_min_records,
+                          bool grp_allowed)
+    {
+        RankPrep p;
+        if (R < 2)
+            return p;
+        if (grp_allowed && grp_eligible(first, (size_t)R)) {
+            p.route = RRDB_ROUTE_RANK_GRP;
+            p.n_groups = build_anchors(dr, R, lo, hi, d_lo, d_hi, &p.d_anch);
+            return p;
+        }
+        if (total > bt_min_records)
+            p.bound_levels = build_bound_table(dr, R, lo, hi, d_lo, d_hi, &p.d_bt_off, &p.d_bt);
+        if (ldst_eligible(first, (size_t)R))
+            p.route = RRDB_ROUTE_RANK_LDST;
+        return p;
     }
 
     /* build the visible view for [start, stop_excl); a null bound is open */
@@ -1434,34 +1514,25 @@ struct HipEngine {
         uint64_t *d_flags = talloc<uint64_t>(total * 8);
         uint64_t *d_pos = talloc<uint64_t>(total * 8);
         last_view.window_records = total;
-        if (R > 1 && grp_eligible()) {
-            uint64_t *d_anch = nullptr;
-            uint64_t n_groups = build_anchors(dr, R, lo, hi, d_lo, d_hi, &d_anch);
-            last_view.rank = RRDB_ROUTE_RANK_GRP;
-            last_view.n_groups = n_groups;
-            launch_rank_grp_view(dr, R, d_lo, d_anch, n_groups, d_order, d_shadow, stream);
-        } else {
-            uint64_t *d_bt_off = nullptr, *d_bt = nullptr;
-            if (R > 1 && total > VIEW_BT_MIN_RECORDS)
-                last_view.bound_levels =
-                    build_bound_table(dr, R, lo, hi, d_lo, d_hi, &d_bt_off, &d_bt);
-            if (ldst_eligible()) {
-                last_view.rank = RRDB_ROUTE_RANK_LDST;
-                launch_rank_ldst(dr, R, d_lo, d_hi, d_wp, total, d_order, d_shadow, d_bt_off,
-                                 d_bt, bt_shift, stream);
-            } else {
-                last_view.rank = RRDB_ROUTE_RANK_GLOBAL;
-                launch_rank(dr, R, d_lo, d_hi, d_wp, total, d_order, d_shadow, d_bt_off, d_bt,
-                            bt_shift, stream);
-            }
-        }
+        const RankPrep rp = prepare_rank(dr, 0, R, lo, hi, d_lo, d_hi, total,
+                                         VIEW_BT_MIN_RECORDS, true);
+        last_view.rank = rp.route;
+        last_view.n_groups = rp.n_groups;
+        last_view.bound_levels = rp.bound_levels;
+        if (rp.route == RRDB_ROUTE_RANK_GRP)
+            launch_rank_grp_view(dr, R, d_lo, rp.d_anch, rp.n_groups, d_order, d_shadow, stream);
+        else if (rp.route == RRDB_ROUTE_RANK_LDST)
+            launch_rank_ldst(dr, R, d_lo, d_hi, d_wp, total, d_order, d_shadow, rp.d_bt_off,
+                             rp.d_bt, bt_shift, stream);
+        else
+            launch_rank(dr, R, d_lo, d_hi, d_wp, total, d_order, d_shadow, rp.d_bt_off, rp.d_bt,
+                        bt_shift, stream);
         launch_visible(dr, d_order, d_shadow, total, d_flags, stream);
         launch_psum(d_flags, d_pos, total, psum_scratch(total), stream);
-        uint64_t lastp = 0, lastf = 0;
-        HIP_OK(hipMemcpyAsync(&lastp, d_pos + total - 1, 8, hipMemcpyDeviceToHost, stream));
-        HIP_OK(hipMemcpyAsync(&lastf, d_flags + total - 1, 8, hipMemcpyDeviceToHost, stream));
+        uint64_t last[2] = {0, 0};
+        scan_tail_async(d_pos, d_flags, total, last, stream);
         HIP_OK(hipStreamSynchronize(stream));
-        uint64_t nv = lastp + lastf;
+        uint64_t nv = last[0] + last[1];
         last_view.visible = nv;
         uint64_t *d_view = nullptr;
         if (nv) {
@@ -1577,13 +1648,12 @@ void rrdb_close(void *h)
         (void)hipFree(b.first);
     if (e->pinned)
         (void)hipHostFree(e->pinned);
-    if (e->pend_sizes)
-        (void)hipHostFree(e->pend_sizes);
-    if (e->pend_stats_h)
-        (void)hipHostFree(e->pend_stats_h);
-    for (auto &x : e->tev)
-        if (x)
+    if (e->kept.sizes) {
+        (void)hipHostFree(e->kept.sizes);
+        (void)hipHostFree(e->kept.stats);
+        for (auto &x : e->kept.ev)
             (void)hipEventDestroy(x);
+    }
     e->server_quit_sync();
     if (e->mg_mb)
         (void)hipHostFree((void *)e->mg_mb);
@@ -1785,27 +1855,20 @@ static int32_t get_core(HipEngine *e, uint64_t nq, const uint8_t *keys, const ui
     uint64_t *d_hit = e->talloc<uint64_t>(nq * 8);
     uint64_t *d_ulen = e->talloc<uint64_t>(nq * 8);
     uint64_t *d_voffs = e->talloc<uint64_t>((nq + 1) * 8);
-    hipEvent_t gev[2];
-    HIP_OK(hipEventCreate(&gev[0]));
-    HIP_OK(hipEventCreate(&gev[1]));
-    HIP_OK(hipEventRecord(gev[0], e->stream));
+    uint64_t last[2] = {0, 0};
+    PhaseEvents<2> gev;
+    gev.record(0, e->stream);
     launch_get(dr, R, d_keys, d_offs, nq, epoch_now, e->data_version, d_status, d_hit, d_ulen,
                nullptr, e->stream);
-    HIP_OK(hipEventRecord(gev[1], e->stream));
+    gev.record(1, e->stream);
     launch_psum(d_ulen, d_voffs, nq, e->psum_scratch(nq), e->stream);
-    uint64_t last_off = 0, last_len = 0;
-    HIP_OK(hipMemcpyAsync(&last_off, d_voffs + nq - 1, 8, hipMemcpyDeviceToHost, e->stream));
-    HIP_OK(hipMemcpyAsync(&last_len, d_ulen + nq - 1, 8, hipMemcpyDeviceToHost, e->stream));
+    scan_tail_async(d_voffs, d_ulen, nq, last, e->stream);
     HIP_OK(hipMemcpyAsync(status.data(), d_status, nq * 4, hipMemcpyDeviceToHost, e->stream));
     HIP_OK(hipStreamSynchronize(e->stream));
-    {
-        float ms;
-        if (hipEventElapsedTime(&ms, gev[0], gev[1]) == hipSuccess)
-            e->phase_ms["get_search"] = ms;
-        (void)hipEventDestroy(gev[0]);
-        (void)hipEventDestroy(gev[1]);
-    }
-    uint64_t total = last_off + last_len;
+    float ms;
+    if (gev.ms(0, 1, &ms))
+        e->phase_ms["get_search"] = ms;
+    uint64_t total = last[0] + last[1];
     std::vector<uint64_t> voffs(nq + 1);
     HIP_OK(hipMemcpy(voffs.data(), d_voffs, nq * 8, hipMemcpyDeviceToHost));
     voffs[nq] = total;
@@ -2118,12 +2181,10 @@ static void scan_batch_gpu(HipEngine *e, HipScanCtx *c, uint32_t epoch_now, rrdb
     uint64_t *d_flags = e->talloc<uint64_t>(w * 8);
     uint64_t *d_npos = e->talloc<uint64_t>(w * 8);
     uint64_t *d_cut = e->talloc<uint64_t>(16);
-    hipEvent_t sev[4];
-    for (auto &x : sev)
-        HIP_OK(hipEventCreate(&x));
-    HIP_OK(hipEventRecord(sev[0], e->stream));
+    PhaseEvents<4> sev;
+    sev.record(0, e->stream);
     launch_scan_state(dr, d_win, w, sp, d_state, d_ksz, d_vsz, e->stream);
-    HIP_OK(hipEventRecord(sev[1], e->stream));
+    sev.record(1, e->stream);
     launch_normal_flags(d_state, w, d_flags, e->stream);
     launch_psum(d_flags, d_npos, w, e->psum_scratch(w), e->stream);
     launch_cutoff(d_npos, d_flags, w, batch_count, d_cut, e->stream);
@@ -2145,10 +2206,8 @@ static void scan_batch_gpu(HipEngine *e, HipScanCtx *c, uint32_t epoch_now, rrdb
         launch_psum(d_ksz, d_koffs, w, e->psum_scratch(w), e->stream);
         launch_psum(d_vsz, d_voffs, w, e->psum_scratch(w), e->stream);
         uint64_t t[4] = {0, 0, 0, 0};
-        HIP_OK(hipMemcpyAsync(&t[0], d_koffs + w - 1, 8, hipMemcpyDeviceToHost, e->stream));
-        HIP_OK(hipMemcpyAsync(&t[1], d_ksz + w - 1, 8, hipMemcpyDeviceToHost, e->stream));
-        HIP_OK(hipMemcpyAsync(&t[2], d_voffs + w - 1, 8, hipMemcpyDeviceToHost, e->stream));
-        HIP_OK(hipMemcpyAsync(&t[3], d_vsz + w - 1, 8, hipMemcpyDeviceToHost, e->stream));
+        scan_tail_async(d_koffs, d_ksz, w, &t[0], e->stream);
+        scan_tail_async(d_voffs, d_vsz, w, &t[2], e->stream);
         HIP_OK(hipStreamSynchronize(e->stream));
         uint64_t kbytes = t[0] + t[1], vbytes = t[2] + t[3];
         uint8_t *d_kout, *d_vout;
@@ -2168,10 +2227,10 @@ static void scan_batch_gpu(HipEngine *e, HipScanCtx *c, uint32_t epoch_now, rrdb
         }
         if (c->return_expire_ts)
             d_ets = e->talloc<int32_t>(n_out * 4);
-        HIP_OK(hipEventRecord(sev[2], e->stream));
+        sev.record(2, e->stream);
         launch_emit_scan(dr, d_win, w, d_state, consumed, d_npos, d_koffs, d_voffs, sp, d_kout,
                          d_vout, d_kooffs, d_vooffs, d_ets, n_out, e->stream);
-        HIP_OK(hipEventRecord(sev[3], e->stream));
+        sev.record(3, e->stream);
         if (c->on_device_out) {
             HIP_OK(hipStreamSynchronize(e->stream));
             out->dev_keys = d_kout;
@@ -2215,15 +2274,12 @@ static void scan_batch_gpu(HipEngine *e, HipScanCtx *c, uint32_t epoch_now, rrdb
     }
     {
         float ms;
-        HIP_OK(hipEventSynchronize(sev[1]));
-        HIP_OK(hipEventElapsedTime(&ms, sev[0], sev[1]));
+        HIP_OK(hipEventSynchronize(sev.ev[1]));
+        HIP_OK(hipEventElapsedTime(&ms, sev.ev[0], sev.ev[1]));
         e->phase_ms["scan_state"] = ms;
-        if (hipEventQuery(sev[3]) == hipSuccess &&
-            hipEventElapsedTime(&ms, sev[2], sev[3]) == hipSuccess)
+        if (hipEventQuery(sev.ev[3]) == hipSuccess && sev.ms(2, 3, &ms))
             e->phase_ms["scan_emit"] = ms;
     }
-    for (auto &x : sev)
-        (void)hipEventDestroy(x);
     e->tfree(d_state);
     e->tfree(d_ksz);
     e->tfree(d_vsz);
@@ -2361,7 +2417,8 @@ int32_t rrdb_scan_count_begin(void *h, const rrdb_scan_request *q, uint32_t epoc
     uint64_t batch_cap = q->batch_size > 0 ? (uint64_t)q->batch_size : (uint64_t)INT32_MAX;
     int R0 = (int)e->runs.size();
     bool single = R0 == 1; /* no merge/shadow needed: plain count kernel */
-    if ((R0 > 1 && !e->grp_eligible()) || batch_cap < total || e->max_iter_count < total)
+    if ((R0 > 1 && !e->grp_eligible(0, (size_t)R0)) || batch_cap < total ||
+        e->max_iter_count < total)
         return RRDB_INVALID_ARGUMENT;
     if (R0 == 0) {
         e->pend_scan.active = true;
@@ -2429,9 +2486,7 @@ int32_t rrdb_scan_count_begin(void *h, const rrdb_scan_request *q, uint32_t epoc
                 nmax = e->runs[r].n;
                 q0 = r;
             }
-        int gs = 4;
-        while ((1ull << (gs + 1)) * (uint64_t)R <= GRP_TARGET && gs < 8)
-            gs++;
+        const int gs = grp_shift(R);
         n_groups = (nmax + (1ull << gs) - 1) >> gs;
         if (n_groups == 0)
             n_groups = 1;
@@ -2541,11 +2596,10 @@ int32_t rrdb_sortkey_count(void *h, const uint8_t *hash_key, uint64_t hklen, uin
         launch_scan_state(e->dev_runs(), view.d, n, sp, d_state, d_ksz, d_vsz, e->stream);
         launch_normal_flags(d_state, n, d_flags, e->stream);
         launch_psum(d_flags, d_npos, n, e->psum_scratch(n), e->stream);
-        uint64_t lastp = 0, lastf = 0;
-        HIP_OK(hipMemcpyAsync(&lastp, d_npos + n - 1, 8, hipMemcpyDeviceToHost, e->stream));
-        HIP_OK(hipMemcpyAsync(&lastf, d_flags + n - 1, 8, hipMemcpyDeviceToHost, e->stream));
+        uint64_t last[2] = {0, 0};
+        scan_tail_async(d_npos, d_flags, n, last, e->stream);
         HIP_OK(hipStreamSynchronize(e->stream));
-        count = (int64_t)(lastp + lastf);
+        count = (int64_t)(last[0] + last[1]);
         e->tfree(d_state);
         e->tfree(d_ksz);
         e->tfree(d_vsz);
@@ -3028,73 +3082,114 @@ int32_t rrdb_last_view_route(void *h, rrdb_view_route *out)
     return RRDB_OK;
 }
 
-/* phase 1 of the compaction (the pipelined-partitions seam; the reference
- * runs per-replica compactions concurrently on THREAD_POOL_COMPACT —
- * pegasus_server_impl.cpp:3373): submit rank + prefix sums + async size
- * reads, NO host-blocking sync.  Caller holds the handle lock. */
-/* The pass merges the window [first, first+n) of e->runs (0 = oldest) into
- * one run that takes the window's place; it is bottommost iff first == 0.
+/* ---- the compaction pass ----
+ * It merges the window [first, first+n) of e->runs (0 = oldest) into one run
+ * that takes the window's place; it is bottommost iff first == 0.
  * win == nullptr is the manual pass: every run, honouring
  * manual_compact.disabled and engine.emit_mode.  A window pass (the caller
  * validated it after flushing) always takes the chunked emit, the only one
- * that knows converted tombstones. */
+ * that knows converted tombstones.  compact_begin's four steps come first. */
 struct CompactWindow {
     size_t first, n;
 };
-static int32_t compact_begin(HipEngine *e, const rrdb_compact_options *opts, uint32_t epoch_now,
-                             const CompactWindow *win = nullptr)
+using CompactPlan = HipEngine::CompactPlan;
+static constexpr uint64_t COMPACT_BT_MIN_RECORDS = 100000; /* bound table above this */
+
+/* step 1, host decisions only: the window, the emit the pass is built for and
+ * which arrays that emit can do without */
+static CompactPlan plan_pass(const HipEngine *e, const rrdb_compact_options *opts,
+                             const CompactWindow *win)
 {
-    if (e->pend.active)
-        return RRDB_INVALID_ARGUMENT;
-    if (engine_flush(e) != RRDB_OK) /* memtable visible to reads */
-        return RRDB_IO_ERROR;
-    e->scratch_reset();
-    rrdb_compact_stats st{};
-    if (!win && e->manual_compact_disabled)
-        return RRDB_INVALID_ARGUMENT;
-    e->activate();
-    e->last_route = {RRDB_ROUTE_NONE, RRDB_ROUTE_NONE};
-    const size_t first = win ? win->first : 0;
-    int R = (int)(win ? win->n : e->runs.size());
-    const bool bottommost = first == 0;
-    const int emit_mode = win ? 2 : e->emit_mode;
-    const RunBuf *wr = e->runs.data() + first; /* the window's runs */
-    uint64_t total = 0;
-    for (int r = 0; r < R; r++)
-        total += wr[r].n;
-    st.input_records = total;
-    if (total == 0) {
-        e->pend = {};
-        e->pend.active = true;
-        e->pend.trivial = true;
-        e->pend.st = st;
-        return RRDB_OK;
-    }
-    /* run ids in order[] are relative to this pointer, i.e. to the window */
-    DevRun *dr = e->dev_runs() + first;
-    /* full-range rank merge */
-    std::vector<uint64_t> lo(R, 0), hi(R);
-    /* lo | hi | wprefix travel as one upload: [R] [R] [R + 1] */
-    std::vector<uint64_t> bounds(3 * (size_t)R + 1, 0);
+    CompactPlan p;
+    p.active = true;
+    p.keep_inputs = opts && opts->keep_inputs;
+    p.first = win ? win->first : 0;
+    p.R = (int)(win ? win->n : e->runs.size());
+    p.bottommost = p.first == 0;
+    p.emit_mode = win ? 2 : e->emit_mode;
+    const RunBuf *wr = e->runs.data() + p.first; /* the window's runs */
+    for (int r = 0; r < p.R; r++)
+        p.total += wr[r].n;
+    p.st.input_records = p.total;
+    p.trivial = p.total == 0;
+    if (p.trivial)
+        return p;
+    /* all-fixed-stride fast mode: every run shares one key and one value
+     * stride (the hashkey-table schema), so output offsets derive from the
+     * keep count — no ksz/vsz arrays, one prefix sum instead of three.  Not
+     * when non-bottommost: tombstone rows (kept or converted) are not fv long.
+     * The fused emit indexes inside a tile in 32 bits, hence the stride cap. */
+    const uint32_t ffk = shared_stride(wr, p.R, &RunBuf::fixed_klen);
+    const uint32_t ffv = shared_stride(wr, p.R, &RunBuf::fixed_vlen_put);
+    if (ffk > 0 && ffv > 0 && p.emit_mode == 2 && p.bottommost && ffk <= EMIT_MAX_STRIDE &&
+        ffv <= EMIT_MAX_STRIDE)
+        p.fk = ffk, p.fv = ffv;
+    /* no default-TTL and no user ops => the filter can never rewrite a
+     * value: skip the changed/new_expire arrays and the patch pass.  Not so
+     * when non-bottommost: an expired PUT is rewritten into a tombstone and
+     * changed[] carries that marker. */
+    p.no_rewrite = e->default_ttl == 0 && e->n_ops == 0 && p.emit_mode == 2 && p.bottommost;
+    return p;
+}
+
+/* step 2: the pass's arena arrays, each only where step 1 left it needed */
+static void alloc_pass_arrays(HipEngine *e, CompactPlan &p)
+{
+    const int R = p.R;
+    const uint64_t total = p.total;
+    const RunBuf *wr = e->runs.data() + p.first;
+    /* rows | lo | hi | wprefix travel as one upload: [R DevRun] [R] [R] [R + 1].
+     * The rows are the pass's own: e->d_runs may be rebuilt before finish. */
+    static_assert(sizeof(DevRun) % 8 == 0, "DevRun rows precede 8-byte bounds");
+    const size_t row_words = sizeof(DevRun) / 8;
+    std::vector<uint64_t> up(R * row_words + 3 * (size_t)R + 1, 0);
+    uint64_t *bounds = up.data() + R * row_words;
     uint64_t acc = 0;
     for (int r = 0; r < R; r++) {
-        hi[r] = wr[r].n;
-        bounds[R + r] = hi[r];
+        const DevRun row = HipEngine::to_dev(wr[r]);
+        memcpy(up.data() + r * row_words, &row, sizeof(row));
+        bounds[R + r] = wr[r].n;
         bounds[2 * R + r] = acc;
         acc += wr[r].n;
     }
     bounds[3 * R] = acc;
-    uint64_t *d_lo = (uint64_t *)e->upload_tmp(bounds.data(), bounds.size() * 8);
-    uint64_t *d_hi = d_lo + R;
-    uint64_t *d_wp = d_hi + R;
-    uint64_t *d_order = e->talloc<uint64_t>(total * 8);
-    e->resolve_phase_events(); /* previous pass's timing, before reuse */
-    e->tev_have_emit = false;
-    if (!e->tev[0])
-        for (auto &x : e->tev)
-            HIP_OK(hipEventCreate(&x));
-    hipEvent_t *ev = e->tev;
+    p.dr = (DevRun *)e->upload_tmp(up.data(), up.size() * 8);
+    p.d_lo = (uint64_t *)(p.dr + R);
+    p.d_hi = p.d_lo + R;
+    p.d_wp = p.d_hi + R;
+    p.d_order = e->talloc<uint64_t>(total * 8);
+    if (!p.no_rewrite) {
+        p.d_changed = e->talloc<uint8_t>(total);
+        p.d_new_expire = e->talloc<uint32_t>(total * 4);
+    }
+    p.d_keepw = e->talloc<uint64_t>(total * 8);
+    if (!p.fk) {
+        /* all-fixed-stride has none of these: its emit scans the keep flags by tile */
+        p.d_ksz = e->talloc<uint64_t>(total * 8);
+        p.d_vsz = e->talloc<uint64_t>(total * 8);
+        p.d_kpos = e->talloc<uint64_t>(total * 8);
+        p.d_koffs = e->talloc<uint64_t>(total * 8);
+        p.d_voffs = e->talloc<uint64_t>(total * 8);
+    } else {
+        p.d_tile_base = e->talloc<uint64_t>(emit_n_tiles(total) * 8);
+    }
+    if (p.emit_mode == 1)
+        p.d_rank_of = e->talloc<uint64_t>(total * 8);
+    /* 8 stat banks: the group rank flushes per-block tallies to bank
+     * blockIdx&7; legacy kernels add to bank 0; finish sums all banks */
+    p.d_stats = e->talloc<CompactStatsDev>(8 * sizeof(CompactStatsDev));
+    HIP_OK(hipMemsetAsync(p.d_stats, 0, 8 * sizeof(CompactStatsDev), e->stream));
+}
 
+/* step 3: one of four rank kernels between ev[0] and ev[1]; the tables it
+ * narrows by are built in front of ev[0] */
+static void rank_pass(HipEngine *e, const CompactPlan &p, uint32_t epoch_now)
+{
+    const int R = p.R;
+    DevRun *dr = p.dr;
+    std::vector<uint64_t> lo(R, 0), hi(R); /* full-range rank merge */
+    for (int r = 0; r < R; r++)
+        hi[r] = e->runs[p.first + r].n;
     CompactParams cp{};
     cp.epoch_now = epoch_now;
     cp.data_version = e->data_version;
@@ -3106,61 +3201,22 @@ static int32_t compact_begin(HipEngine *e, const rrdb_compact_options *opts, uin
     cp.n_ops = e->n_ops;
     cp.rules = e->d_rules;
     cp.pats = e->d_pats;
-    cp.bottommost = bottommost ? 1 : 0;
-
-    /* all-fixed-stride fast mode: every run shares one key and one value
-     * stride (the hashkey-table schema), so output offsets derive from the
-     * keep count — the ksz/vsz arrays and two of the three full-length
-     * prefix sums are skipped entirely */
-    uint64_t ffk = shared_stride(wr, R, &RunBuf::fixed_klen);
-    uint64_t ffv = shared_stride(wr, R, &RunBuf::fixed_vlen_put);
-    /* a non-bottommost output can hold tombstones (kept or converted), whose
-     * rows are not fv long: it always takes the per-row-size path */
-    bool fixed_emit = ffk > 0 && ffv > 0 && emit_mode == 2 && bottommost;
-    /* the fused emit indexes inside a tile in 32 bits */
-    if (ffk > EMIT_MAX_STRIDE || ffv > EMIT_MAX_STRIDE)
-        fixed_emit = false;
-    /* no default-TTL and no user ops => the filter can never rewrite a
-     * value: skip the changed/new_expire arrays and the patch pass.  Not so
-     * when non-bottommost: an expired PUT is rewritten into a tombstone and
-     * changed[] carries that marker. */
-    bool no_rewrite = e->default_ttl == 0 && e->n_ops == 0 && emit_mode == 2 && bottommost;
-    uint8_t *d_changed = no_rewrite ? nullptr : e->talloc<uint8_t>(total);
-    uint32_t *d_new_expire = no_rewrite ? nullptr : e->talloc<uint32_t>(total * 4);
-    uint64_t *d_ksz = fixed_emit ? nullptr : e->talloc<uint64_t>(total * 8);
-    uint64_t *d_vsz = fixed_emit ? nullptr : e->talloc<uint64_t>(total * 8);
-    uint64_t *d_keepw = e->talloc<uint64_t>(total * 8);
-    /* all-fixed-stride: the emit scans the keep flags itself, tile by tile;
-     * only the per-tile counts are summed here */
-    uint64_t *d_kpos = fixed_emit ? nullptr : e->talloc<uint64_t>(total * 8);
-    const uint64_t n_tiles = emit_n_tiles(total);
-    uint32_t *d_tile_cnt = fixed_emit ? e->talloc<uint32_t>(n_tiles * 4) : nullptr;
-    uint64_t *d_tile_base = fixed_emit ? e->talloc<uint64_t>(n_tiles * 8) : nullptr;
-    uint64_t *d_n_out = fixed_emit ? e->talloc<uint64_t>(8) : nullptr;
-    uint64_t *d_koffs = fixed_emit ? nullptr : e->talloc<uint64_t>(total * 8);
-    uint64_t *d_voffs = fixed_emit ? nullptr : e->talloc<uint64_t>(total * 8);
-    uint64_t *d_rank_of = emit_mode == 1 ? e->talloc<uint64_t>(total * 8) : nullptr;
-    /* 8 stat banks: the group rank flushes per-block tallies to bank
-     * blockIdx&7; legacy kernels add to bank 0; finish sums all banks */
-    CompactStatsDev *d_stats = e->talloc<CompactStatsDev>(8 * sizeof(CompactStatsDev));
-    HIP_OK(hipMemsetAsync(d_stats, 0, 8 * sizeof(CompactStatsDev), e->stream));
-    if (e->rank_mode == 1 && R > 1 && R <= RRDB_MAX_RUNS && emit_mode == 2) {
+    cp.bottommost = p.bottommost ? 1 : 0;
+    hipEvent_t *ev = e->kept.ev;
+    if (e->rank_mode == 1 && R > 1 && R <= RRDB_MAX_RUNS && p.emit_mode == 2) {
         /* LDS-staged block rank: shift-8 bound table + per-run block counts.
          * The kernel keeps per-run window tables of RRDB_MAX_RUNS entries in
          * LDS; more runs than that take the global rank below */
-        e->last_route.rank = RRDB_ROUTE_RANK_LDS;
-        uint64_t *d_bt8_off = nullptr, *d_bt8 = nullptr;
-        {
-            uint64_t *c_off = nullptr, *c_bt = nullptr;
-            uint64_t wmax = 0;
-            for (int r = 0; r < R; r++)
-                wmax = std::max(wmax, hi[r] - lo[r]);
-            if ((wmax >> 14) > 8)
-                e->build_bound_table_level(dr, R, lo, hi, d_lo, d_hi, 14, nullptr, nullptr, 0,
-                                           &c_off, &c_bt);
-            e->build_bound_table_level(dr, R, lo, hi, d_lo, d_hi, 8, c_off, c_bt, 14, &d_bt8_off,
-                                       &d_bt8);
-        }
+        e->kept.route.rank = RRDB_ROUTE_RANK_LDS;
+        uint64_t *c_off = nullptr, *c_bt = nullptr, *d_bt8_off = nullptr, *d_bt8 = nullptr;
+        uint64_t wmax = 0;
+        for (int r = 0; r < R; r++)
+            wmax = std::max(wmax, hi[r] - lo[r]);
+        if ((wmax >> 14) > 8)
+            e->build_bound_table_level(dr, R, lo, hi, p.d_lo, p.d_hi, 14, nullptr, nullptr, 0,
+                                       &c_off, &c_bt);
+        e->build_bound_table_level(dr, R, lo, hi, p.d_lo, p.d_hi, 8, c_off, c_bt, 14,
+                                   &d_bt8_off, &d_bt8);
         std::vector<uint64_t> blkp(R + 1);
         uint64_t nb = 0;
         for (int r = 0; r < R; r++) {
@@ -3170,241 +3226,243 @@ static int32_t compact_begin(HipEngine *e, const rrdb_compact_options *opts, uin
         blkp[R] = nb;
         uint64_t *d_blkp = (uint64_t *)e->upload_tmp(blkp.data(), (R + 1) * 8);
         HIP_OK(hipEventRecord(ev[0], e->stream));
-        launch_rank_compact_lds(dr, R, d_lo, d_hi, d_blkp, nb, cp, d_bt8_off, d_bt8, d_order,
-                                d_keepw, d_changed, d_new_expire, d_ksz, d_vsz, d_stats,
-                                e->stream);
+        launch_rank_compact_lds(dr, R, p.d_lo, p.d_hi, d_blkp, nb, cp, d_bt8_off, d_bt8,
+                                p.d_order, p.d_keepw, p.d_changed, p.d_new_expire, p.d_ksz,
+                                p.d_vsz, p.d_stats, e->stream);
         HIP_OK(hipEventRecord(ev[1], e->stream));
-    } else if (R > 1 && emit_mode != 1 && e->grp_eligible(first, (size_t)R)) {
-        /* group-streaming rank: no bound table; anchors partition the runs */
-        e->last_route.rank = RRDB_ROUTE_RANK_GRP;
-        uint64_t *d_anch = nullptr;
-        uint64_t n_groups = e->build_anchors(dr, R, lo, hi, d_lo, d_hi, &d_anch);
-        HIP_OK(hipEventRecord(ev[0], e->stream));
-        launch_rank_grp_compact(dr, R, d_lo, d_anch, n_groups, cp, d_order, d_keepw, d_changed,
-                                d_new_expire, d_ksz, d_vsz, d_stats, e->grp_blocks, e->stream);
-        HIP_OK(hipEventRecord(ev[1], e->stream));
-    } else {
-    uint64_t *d_bt_off = nullptr, *d_bt = nullptr;
-    if (R > 1 && total > 100000)
-        e->build_bound_table(dr, R, lo, hi, d_lo, d_hi, &d_bt_off, &d_bt);
+        return;
+    }
+    /* the input-major emit needs rank_of[], which the group rank does not write */
+    const HipEngine::RankPrep rp =
+        e->prepare_rank(dr, p.first, R, lo, hi, p.d_lo, p.d_hi, p.total, COMPACT_BT_MIN_RECORDS,
+                        p.emit_mode != 1);
+    e->kept.route.rank = rp.route;
     HIP_OK(hipEventRecord(ev[0], e->stream));
-    bool ldst_ok = R > 1 && e->ldst_eligible(first, (size_t)R);
-    e->last_route.rank = ldst_ok ? RRDB_ROUTE_RANK_LDST : RRDB_ROUTE_RANK_GLOBAL;
-    if (ldst_ok)
-        launch_rank_compact_ldst(dr, R, d_lo, d_hi, d_wp, total, cp, d_order, d_keepw,
-                                 d_changed, d_new_expire, d_ksz, d_vsz, d_rank_of, d_bt_off,
-                                 d_bt, e->bt_shift, d_stats, e->stream);
+    if (rp.route == RRDB_ROUTE_RANK_GRP)
+        launch_rank_grp_compact(dr, R, p.d_lo, rp.d_anch, rp.n_groups, cp, p.d_order, p.d_keepw,
+                                p.d_changed, p.d_new_expire, p.d_ksz, p.d_vsz, p.d_stats,
+                                e->grp_blocks, e->stream);
+    else if (rp.route == RRDB_ROUTE_RANK_LDST)
+        launch_rank_compact_ldst(dr, R, p.d_lo, p.d_hi, p.d_wp, p.total, cp, p.d_order,
+                                 p.d_keepw, p.d_changed, p.d_new_expire, p.d_ksz, p.d_vsz,
+                                 p.d_rank_of, rp.d_bt_off, rp.d_bt, e->bt_shift, p.d_stats,
+                                 e->stream);
     else
-        launch_rank_compact(dr, R, d_lo, d_hi, d_wp, total, cp, d_order, d_keepw, d_changed,
-                            d_new_expire, d_ksz, d_vsz, d_rank_of, d_bt_off, d_bt, e->bt_shift,
-                            d_stats, e->stream);
+        launch_rank_compact(dr, R, p.d_lo, p.d_hi, p.d_wp, p.total, cp, p.d_order, p.d_keepw,
+                            p.d_changed, p.d_new_expire, p.d_ksz, p.d_vsz, p.d_rank_of,
+                            rp.d_bt_off, rp.d_bt, e->bt_shift, p.d_stats, e->stream);
     HIP_OK(hipEventRecord(ev[1], e->stream));
-    }
-    HIP_OK(hipEventRecord(ev[2], e->stream));
-    if (!e->pend_stats_h)
-        HIP_OK(hipHostMalloc((void **)&e->pend_stats_h, 8 * sizeof(CompactStatsDev)));
-    HIP_OK(hipMemcpyAsync(e->pend_stats_h, d_stats, 8 * sizeof(CompactStatsDev),
+}
+
+/* step 4: the size scans, and the stats and the six sizes (one when
+ * all-fixed-stride) on their way to the pinned targets finish reads */
+static void submit_sizes(HipEngine *e, const CompactPlan &p)
+{
+    const uint64_t total = p.total;
+    HIP_OK(hipEventRecord(e->kept.ev[2], e->stream));
+    HIP_OK(hipMemcpyAsync(e->kept.stats, p.d_stats, 8 * sizeof(CompactStatsDev),
                           hipMemcpyDeviceToHost, e->stream));
-    if (fixed_emit) {
-        launch_keep_tile_scan(d_keepw, total, d_tile_cnt, d_tile_base, d_n_out, e->stream);
-    } else {
-        launch_psum(d_keepw, d_kpos, total, e->psum_scratch(total), e->stream);
-        launch_psum(d_ksz, d_koffs, total, e->psum_scratch(total), e->stream);
-        launch_psum(d_vsz, d_voffs, total, e->psum_scratch(total), e->stream);
-    }
-    if (!e->pend_sizes)
-        HIP_OK(hipHostMalloc((void **)&e->pend_sizes, 6 * 8));
-    uint64_t *t = e->pend_sizes;
+    uint64_t *t = e->kept.sizes;
     memset(t, 0, 6 * 8);
-    if (fixed_emit) {
-        /* the scan's grand total is the whole keep count: t[1] stays 0 */
+    if (p.fk) {
+        /* only the per-tile keep counts are summed here; the scan's grand
+         * total is the whole keep count: t[1] stays 0 */
+        const uint64_t n_tiles = emit_n_tiles(total);
+        uint32_t *d_tile_cnt = e->talloc<uint32_t>(n_tiles * 4);
+        uint64_t *d_n_out = e->talloc<uint64_t>(8);
+        launch_keep_tile_scan(p.d_keepw, total, d_tile_cnt, p.d_tile_base, d_n_out, e->stream);
         HIP_OK(hipMemcpyAsync(&t[0], d_n_out, 8, hipMemcpyDeviceToHost, e->stream));
-    } else {
-        HIP_OK(hipMemcpyAsync(&t[0], d_kpos + total - 1, 8, hipMemcpyDeviceToHost, e->stream));
-        HIP_OK(hipMemcpyAsync(&t[1], d_keepw + total - 1, 8, hipMemcpyDeviceToHost, e->stream));
-        HIP_OK(hipMemcpyAsync(&t[2], d_koffs + total - 1, 8, hipMemcpyDeviceToHost, e->stream));
-        HIP_OK(hipMemcpyAsync(&t[3], d_ksz + total - 1, 8, hipMemcpyDeviceToHost, e->stream));
-        HIP_OK(hipMemcpyAsync(&t[4], d_voffs + total - 1, 8, hipMemcpyDeviceToHost, e->stream));
-        HIP_OK(hipMemcpyAsync(&t[5], d_vsz + total - 1, 8, hipMemcpyDeviceToHost, e->stream));
+        return;
     }
-    e->pend = {};
-    e->pend.active = true;
-    e->pend.keep_inputs = opts && opts->keep_inputs;
-    e->pend.R = R;
-    e->pend.first = first;
-    e->pend.bottommost = bottommost;
-    e->pend.emit_mode = emit_mode;
-    e->pend.total = total;
-    e->pend.dr = dr;
-    e->pend.d_wp = d_wp;
-    e->pend.d_order = d_order;
-    e->pend.d_keepw = d_keepw;
-    e->pend.d_changed = d_changed;
-    e->pend.d_new_expire = d_new_expire;
-    e->pend.d_kpos = d_kpos;
-    e->pend.d_koffs = d_koffs;
-    e->pend.d_voffs = d_voffs;
-    e->pend.d_rank_of = d_rank_of;
-    e->pend.d_stats = d_stats;
-    e->pend.d_tile_base = d_tile_base;
-    e->pend.fk = fixed_emit ? (uint32_t)ffk : 0;
-    e->pend.fv = fixed_emit ? (uint32_t)ffv : 0;
-    e->pend.no_rewrite = no_rewrite;
-    for (int i = 0; i < 6; i++)
-        e->pend.ev[i] = ev[i];
-    e->pend.st = st;
-    e->arena_pin(); /* reads between begin/finish must not reuse pend buffers */
-    (void)d_lo;
-    (void)d_hi;
-    (void)d_ksz;
-    (void)d_vsz;
+    launch_psum(p.d_keepw, p.d_kpos, total, e->psum_scratch(total), e->stream);
+    launch_psum(p.d_ksz, p.d_koffs, total, e->psum_scratch(total), e->stream);
+    launch_psum(p.d_vsz, p.d_voffs, total, e->psum_scratch(total), e->stream);
+    scan_tail_async(p.d_kpos, p.d_keepw, total, &t[0], e->stream);
+    scan_tail_async(p.d_koffs, p.d_ksz, total, &t[2], e->stream);
+    scan_tail_async(p.d_voffs, p.d_vsz, total, &t[4], e->stream);
+}
+
+/* phase 1 (the pipelined-partitions seam; the reference runs per-replica
+ * compactions concurrently on THREAD_POOL_COMPACT —
+ * pegasus_server_impl.cpp:3373): submit rank + prefix sums + async size
+ * reads, NO host-blocking sync.  Caller holds the handle lock. */
+static int32_t compact_begin(HipEngine *e, const rrdb_compact_options *opts, uint32_t epoch_now,
+                             const CompactWindow *win = nullptr)
+{
+    if (e->pend.active)
+        return RRDB_INVALID_ARGUMENT;
+    if (engine_flush(e) != RRDB_OK) /* memtable visible to reads */
+        return RRDB_IO_ERROR;
+    e->scratch_reset();
+    if (!win && e->manual_compact_disabled)
+        return RRDB_INVALID_ARGUMENT;
+    e->activate();
+    e->kept.route = {RRDB_ROUTE_NONE, RRDB_ROUTE_NONE};
+    CompactPlan p = plan_pass(e, opts, win);
+    if (!p.trivial) {
+        e->kept.init();
+        e->resolve_phase_events(); /* previous pass's timing, before reuse */
+        e->kept.have_emit = false;
+        alloc_pass_arrays(e, p);
+        rank_pass(e, p, epoch_now);
+        submit_sizes(e, p);
+        e->arena_pin(); /* reads between begin/finish must not reuse the plan's arrays */
+    }
+    e->pend = p;
     return RRDB_OK;
+}
+
+/* finish, after its sync: output sizes, and the summed stat banks into p.st */
+struct PassSizes {
+    uint64_t n_out, kbytes, vbytes;
+    bool tombstone_out; /* a tombstone was emitted (non-bottommost only) */
+};
+static PassSizes read_sizes_and_stats(const HipEngine *e, CompactPlan &p)
+{
+    const uint64_t *t = e->kept.sizes;
+    PassSizes s;
+    s.n_out = t[0] + t[1];
+    s.kbytes = p.fk ? s.n_out * p.fk : t[2] + t[3];
+    s.vbytes = p.fk ? s.n_out * p.fv : t[4] + t[5];
+    CompactStatsDev hs{};
+    for (int b = 0; b < 8; b++) {
+        hs.shadowed += e->kept.stats[b].shadowed;
+        hs.tombstones += e->kept.stats[b].tombstones;
+        hs.expired += e->kept.stats[b].expired;
+        hs.filtered += e->kept.stats[b].filtered;
+    }
+    p.st.output_records = s.n_out;
+    p.st.expired = hs.expired;
+    p.st.filtered = hs.filtered;
+    /* non-bottommost: no tombstone is dropped (each is in output_records);
+     * expired/filtered count the conversions */
+    p.st.tombstones = p.bottommost ? hs.tombstones : 0;
+    p.st.shadowed = hs.shadowed;
+    p.st.output_bytes = s.kbytes + s.vbytes;
+    s.tombstone_out = !p.bottommost && hs.tombstones + hs.expired + hs.filtered > 0;
+    return s;
+}
+
+/* the merged run's strides: keys, values and PUT values come out as
+ * verbatim-length copies, so a stride every input shares survives */
+static void output_strides(const RunBuf *wr, int R, bool tombstone_out, RunBuf *nr)
+{
+    nr->fixed_klen = shared_stride(wr, R, &RunBuf::fixed_klen);
+    nr->fixed_vlen = shared_stride(wr, R, &RunBuf::fixed_vlen);
+    nr->fixed_vlen_put = shared_stride(wr, R, &RunBuf::fixed_vlen_put);
+    if (tombstone_out)
+        nr->fixed_vlen = 0; /* kept, or converted with an empty value: no plain stride */
+    else if (!nr->fixed_vlen)
+        nr->fixed_vlen = nr->fixed_vlen_put; /* only PUTs came out */
+}
+
+/* the emit the plan was built for, between ev[3] and ev[4].  fk and
+ * no_rewrite imply the chunked emit (plan_pass). */
+static void emit_pass(HipEngine *e, const CompactPlan &p, const PassSizes &s, const RunBuf &nr)
+{
+    HIP_OK(hipEventRecord(e->kept.ev[3], e->stream));
+    if (p.fk) {
+        /* all-fixed-stride: scan, row columns and both copies in one
+         * kernel over the tiles submit_sizes counted */
+        e->kept.route.emit = RRDB_ROUTE_EMIT_CHUNKED_FIXED;
+        launch_emit_fixed_fused(p.dr, p.R, p.d_order, p.total, p.d_keepw, p.d_tile_base,
+                                p.d_changed, p.d_new_expire, e->data_version, p.fk, p.fv, s.n_out,
+                                nr.keys, nr.vals, nr.koff, nr.voff, nr.sk, e->stream);
+    } else if (p.emit_mode == 2) {
+        e->kept.route.emit = RRDB_ROUTE_EMIT_CHUNKED;
+        uint64_t *d_row_ksrc = e->talloc<uint64_t>(s.n_out * 8);
+        uint64_t *d_row_vsrc = e->talloc<uint64_t>(s.n_out * 8);
+        uint32_t *d_row_patch = e->talloc<uint32_t>(s.n_out * 4);
+        uint32_t *d_row_expire = e->talloc<uint32_t>(s.n_out * 4);
+        uint64_t kanch = (((s.kbytes + 15) >> 4) >> 6) + 1;
+        uint64_t vanch = (((s.vbytes + 15) >> 4) >> 6) + 1;
+        uint64_t *d_kanchor = e->talloc<uint64_t>(kanch * 8);
+        uint64_t *d_vanchor = e->talloc<uint64_t>(vanch * 8);
+        launch_emit_compact_chunked(p.dr, p.d_order, p.total, p.d_keepw, p.d_changed,
+                                    p.d_new_expire, p.d_kpos, p.d_koffs, p.d_voffs,
+                                    e->data_version, s.n_out, s.kbytes, s.vbytes, d_row_ksrc,
+                                    d_row_vsrc, d_row_patch, d_row_expire, nr.keys, nr.vals,
+                                    nr.koff, nr.voff, nr.sk, d_kanchor, d_vanchor, e->stream);
+    } else if (p.emit_mode == 1) {
+        e->kept.route.emit = RRDB_ROUTE_EMIT_INPUT;
+        launch_emit_compact_inmajor(p.dr, p.R, p.d_wp, p.total, p.d_rank_of, p.d_keepw,
+                                    p.d_changed, p.d_new_expire, p.d_kpos, p.d_koffs, p.d_voffs,
+                                    e->data_version, nr.keys, nr.vals, nr.koff, nr.voff, nr.sk,
+                                    s.n_out, e->stream);
+    } else {
+        e->kept.route.emit = RRDB_ROUTE_EMIT_RANK;
+        launch_emit_compact(p.dr, p.d_order, p.total, p.d_keepw, p.d_changed, p.d_new_expire,
+                            p.d_kpos, p.d_koffs, p.d_voffs, e->data_version, nr.keys, nr.vals,
+                            nr.koff, nr.voff, nr.sk, s.n_out, e->stream);
+    }
+    HIP_OK(hipEventRecord(e->kept.ev[4], e->stream));
+    e->kept.have_emit = true;
+}
+
+/* only the window's runs go; the merged run (when it has a record) takes
+ * their place at index `first`, older and newer runs stay where they are */
+static void replace_window(HipEngine *e, const CompactPlan &p, RunBuf &nr)
+{
+    e->before_run_free();
+    for (int r = 0; r < p.R; r++)
+        e->free_run(e->runs[p.first + r]);
+    e->runs.erase(e->runs.begin() + p.first, e->runs.begin() + p.first + p.R);
+    if (nr.n > 0) {
+        e->finish_run(nr, nullptr, RunAlloc::Abort, e->bloom_enabled);
+        e->runs.insert(e->runs.begin() + p.first, nr);
+    }
+    e->runs_changed();
 }
 
 /* phase 2: wait for the submitted work, allocate + emit the output run,
  * collect stats.  Caller holds the handle lock. */
 static int32_t compact_finish(HipEngine *e, rrdb_compact_stats *stats)
 {
-    if (!e->pend.active)
+    CompactPlan &p = e->pend;
+    if (!p.active)
         return RRDB_INVALID_ARGUMENT;
     e->activate();
-    e->pend.active = false;
+    p.active = false;
     e->arena_unpin();
-    rrdb_compact_stats st = e->pend.st;
-    if (e->pend.trivial) {
-        if (stats)
-            *stats = st;
-        return RRDB_OK;
-    }
-    int R = e->pend.R;
-    uint64_t total = e->pend.total;
-    DevRun *dr = e->pend.dr;
-    uint64_t *d_wp = e->pend.d_wp, *d_order = e->pend.d_order, *d_keepw = e->pend.d_keepw;
-    uint8_t *d_changed = e->pend.d_changed;
-    uint32_t *d_new_expire = e->pend.d_new_expire;
-    uint64_t *d_kpos = e->pend.d_kpos, *d_koffs = e->pend.d_koffs, *d_voffs = e->pend.d_voffs;
-    uint64_t *d_rank_of = e->pend.d_rank_of;
-    CompactStatsDev *d_stats = e->pend.d_stats;
-    (void)d_stats;
-    hipEvent_t *ev = e->tev;
-    /* wait for the submitted merge phase only (rank + prefix sums + the
-     * async size/stats reads — all of this stream's pending work) */
-    HIP_OK(hipStreamSynchronize(e->stream));
-    uint64_t *t = e->pend_sizes;
-    uint64_t n_out = t[0] + t[1];
-    uint64_t kbytes = e->pend.fk ? n_out * e->pend.fk : t[2] + t[3];
-    uint64_t vbytes = e->pend.fk ? n_out * e->pend.fv : t[4] + t[5];
-
-    CompactStatsDev *hsb = e->pend_stats_h;
-    CompactStatsDev hs{};
-    for (int b = 0; b < 8; b++) {
-        hs.shadowed += hsb[b].shadowed;
-        hs.tombstones += hsb[b].tombstones;
-        hs.expired += hsb[b].expired;
-        hs.filtered += hsb[b].filtered;
-        hs.output_records += hsb[b].output_records;
-    }
-    st.output_records = n_out;
-    st.expired = hs.expired;
-    st.filtered = hs.filtered;
-    /* non-bottommost: no tombstone is dropped (each is in output_records);
-     * expired/filtered count the conversions */
-    st.tombstones = e->pend.bottommost ? hs.tombstones : 0;
-    st.shadowed = hs.shadowed;
-    st.output_bytes = kbytes + vbytes;
-    const size_t first = e->pend.first;
-    const RunBuf *wr = e->runs.data() + first; /* the window's runs */
-
-    RunBuf nr;
-    bool keep_inputs = e->pend.keep_inputs;
-    if (n_out > 0) {
-        /* keys, values and PUT values come out as verbatim-length copies */
-        nr.fixed_klen = shared_stride(wr, R, &RunBuf::fixed_klen);
-        nr.fixed_vlen = shared_stride(wr, R, &RunBuf::fixed_vlen);
-        nr.fixed_vlen_put = shared_stride(wr, R, &RunBuf::fixed_vlen_put);
-        if (e->pend.bottommost) {
-            /* the merged output holds only PUTs: its plain stride equals
-             * the put-stride */
-            if (!nr.fixed_vlen)
-                nr.fixed_vlen = nr.fixed_vlen_put;
-        } else if (hs.tombstones + hs.expired + hs.filtered > 0) {
-            /* a tombstone was emitted (kept, or converted with an empty
-             * value): the output has no plain value stride */
-            nr.fixed_vlen = 0;
-        } else if (!nr.fixed_vlen) {
-            nr.fixed_vlen = nr.fixed_vlen_put; /* only PUTs came out */
+    if (!p.trivial) {
+        /* wait for the submitted merge phase only (rank + prefix sums + the
+         * async size/stats reads — all of this stream's pending work) */
+        HIP_OK(hipStreamSynchronize(e->stream));
+        const PassSizes s = read_sizes_and_stats(e, p);
+        RunBuf nr;
+        if (s.n_out > 0) {
+            output_strides(e->runs.data() + p.first, p.R, s.tombstone_out, &nr);
+            /* keep_inputs drops the output at the end of the pass: arena memory */
+            e->alloc_base(nr, s.n_out, s.kbytes, s.vbytes,
+                          p.keep_inputs ? RunAlloc::Arena : RunAlloc::Abort);
+            emit_pass(e, p, s, nr);
+            /* the swap below frees the input runs the emit reads: drain.
+             * keep_inputs (repeatable-pass, benchmarking) drops the output
+             * instead and returns with the emit in flight — later partitions'
+             * finishes overlap it; stream order protects the arena reuse */
+            if (!p.keep_inputs)
+                HIP_OK(hipStreamSynchronize(e->stream));
         }
-        /* keep_inputs drops the output at the end of the pass: arena memory */
-        e->alloc_base(nr, n_out, kbytes, vbytes, keep_inputs ? RunAlloc::Arena : RunAlloc::Abort);
-        HIP_OK(hipEventRecord(ev[3], e->stream));
-        /* fk and no_rewrite imply the chunked emit (compact_begin) */
-        if (e->pend.fk) {
-            /* all-fixed-stride: scan, row columns and both copies in one
-             * kernel over the tiles compact_begin counted */
-            e->last_route.emit = RRDB_ROUTE_EMIT_CHUNKED_FIXED;
-            launch_emit_fixed_fused(dr, R, d_order, total, d_keepw, e->pend.d_tile_base,
-                                    d_changed, d_new_expire, e->data_version, e->pend.fk,
-                                    e->pend.fv, n_out, nr.keys, nr.vals, nr.koff, nr.voff, nr.sk,
-                                    e->stream);
-        } else if (e->pend.emit_mode == 2) {
-            e->last_route.emit = RRDB_ROUTE_EMIT_CHUNKED;
-            uint64_t *d_row_ksrc = e->talloc<uint64_t>(n_out * 8);
-            uint64_t *d_row_vsrc = e->talloc<uint64_t>(n_out * 8);
-            uint32_t *d_row_patch = e->talloc<uint32_t>(n_out * 4);
-            uint32_t *d_row_expire = e->talloc<uint32_t>(n_out * 4);
-            uint64_t kanch = (((kbytes + 15) >> 4) >> 6) + 1;
-            uint64_t vanch = (((vbytes + 15) >> 4) >> 6) + 1;
-            uint64_t *d_kanchor = e->talloc<uint64_t>(kanch * 8);
-            uint64_t *d_vanchor = e->talloc<uint64_t>(vanch * 8);
-            launch_emit_compact_chunked(dr, d_order, total, d_keepw, d_changed, d_new_expire,
-                                        d_kpos, d_koffs, d_voffs, e->data_version, n_out, kbytes,
-                                        vbytes, d_row_ksrc, d_row_vsrc, d_row_patch,
-                                        d_row_expire, nr.keys, nr.vals, nr.koff, nr.voff, nr.sk,
-                                        d_kanchor, d_vanchor, e->stream);
-        } else if (e->pend.emit_mode == 1) {
-            e->last_route.emit = RRDB_ROUTE_EMIT_INPUT;
-            launch_emit_compact_inmajor(dr, R, d_wp, total, d_rank_of, d_keepw, d_changed,
-                                        d_new_expire, d_kpos, d_koffs, d_voffs,
-                                        e->data_version, nr.keys, nr.vals, nr.koff, nr.voff,
-                                        nr.sk, n_out, e->stream);
-        } else {
-            e->last_route.emit = RRDB_ROUTE_EMIT_RANK;
-            launch_emit_compact(dr, d_order, total, d_keepw, d_changed, d_new_expire, d_kpos,
-                                d_koffs, d_voffs, e->data_version, nr.keys, nr.vals, nr.koff,
-                                nr.voff, nr.sk, n_out, e->stream);
-        }
-        HIP_OK(hipEventRecord(ev[4], e->stream));
-        e->tev_have_emit = true;
-        if (!keep_inputs) {
-            /* the swap below frees the input runs the emit reads: drain */
-            HIP_OK(hipStreamSynchronize(e->stream));
-        }
-        /* keep_inputs (repeatable-pass) mode returns with the emit still
-         * in flight on this engine's stream — later partitions' finishes
-         * overlap it; stream order protects this engine's arena reuse.
-         * Timing is resolved lazily by phase_ms(). */
-    }
-    e->tev_live = true;
-    /* arena temporaries (d_order, flags, sums, keep_inputs outputs) are
-     * reclaimed at the next scratch_reset */
-    if (keep_inputs) {
-        /* benchmarking: the pass ran in full; drop the output, keep inputs */
-    } else {
-        e->before_run_free();
-        /* only the window's runs go; the merged run takes their place at
-         * index `first`, older and newer runs stay where they are */
-        for (int r = 0; r < R; r++)
-            e->free_run(e->runs[first + r]);
-        e->runs.erase(e->runs.begin() + first, e->runs.begin() + first + R);
-        if (n_out > 0) {
-            e->finish_run(nr, nullptr, RunAlloc::Abort, e->bloom_enabled);
-            e->runs.insert(e->runs.begin() + first, nr);
-        }
-        e->runs_changed();
+        e->kept.ev_live = true; /* timing is resolved lazily by phase_ms() */
+        if (!p.keep_inputs)
+            replace_window(e, p, nr);
     }
     if (stats)
-        *stats = st;
+        *stats = p.st;
     return RRDB_OK;
+}
+
+/* a whole pass; a refused begin leaves zeroed stats */
+static int32_t compact_pass(HipEngine *e, const rrdb_compact_options *opts, uint32_t epoch_now,
+                            const CompactWindow *win, rrdb_compact_stats *stats)
+{
+    int32_t rc = compact_begin(e, opts, epoch_now, win);
+    if (rc != RRDB_OK) {
+        if (stats)
+            *stats = rrdb_compact_stats{};
+        return rc;
+    }
+    return compact_finish(e, stats);
 }
 
 int32_t rrdb_manual_compact(void *h, const rrdb_compact_options *opts, uint32_t epoch_now,
@@ -3412,13 +3470,7 @@ int32_t rrdb_manual_compact(void *h, const rrdb_compact_options *opts, uint32_t 
 {
     auto *e = (HipEngine *)h;
     std::lock_guard<std::mutex> g(e->mu);
-    int32_t rc = compact_begin(e, opts, epoch_now);
-    if (rc != RRDB_OK) {
-        if (stats)
-            *stats = rrdb_compact_stats{};
-        return rc;
-    }
-    return compact_finish(e, stats);
+    return compact_pass(e, opts, epoch_now, nullptr, stats);
 }
 
 int32_t rrdb_manual_compact_begin(void *h, const rrdb_compact_options *opts, uint32_t epoch_now)
@@ -3437,27 +3489,13 @@ int32_t rrdb_manual_compact_finish(void *h, rrdb_compact_stats *stats)
 
 /* ---- engine-only extensions (include/rrdb_engine_ext.h) ---- */
 
-/* window pass under the handle lock; the caller flushed and validated */
-static int32_t compact_window(HipEngine *e, size_t first, size_t n, uint32_t epoch_now,
-                              rrdb_compact_stats *stats)
-{
-    CompactWindow w{first, n};
-    int32_t rc = compact_begin(e, nullptr, epoch_now, &w);
-    if (rc != RRDB_OK) {
-        if (stats)
-            *stats = rrdb_compact_stats{};
-        return rc;
-    }
-    return compact_finish(e, stats);
-}
-
 int32_t rrdb_last_compact_route(void *h, rrdb_compact_route *out)
 {
     auto *e = (HipEngine *)h;
     if (!out)
         return RRDB_INVALID_ARGUMENT;
     std::lock_guard<std::mutex> g(e->mu);
-    *out = e->last_route;
+    *out = e->kept.route;
     return RRDB_OK;
 }
 
@@ -3475,7 +3513,8 @@ int32_t rrdb_compact_runs(void *h, uint64_t first_run, uint64_t n_runs, uint32_t
     uint64_t R = e->runs.size();
     if (n_runs == 0 || first_run >= R || n_runs > R - first_run)
         return RRDB_INVALID_ARGUMENT;
-    return compact_window(e, (size_t)first_run, (size_t)n_runs, epoch_now, stats);
+    const CompactWindow w{(size_t)first_run, (size_t)n_runs};
+    return compact_pass(e, nullptr, epoch_now, &w, stats);
 }
 
 /* Size-tiered pick over the age-ordered run list: start from the two newest
@@ -3510,7 +3549,8 @@ int32_t rrdb_auto_compact(void *h, uint32_t epoch_now, uint64_t *first_run_out,
         s--;
         acc += e->runs[s].n;
     }
-    int32_t rc = compact_window(e, s, R - s, epoch_now, stats);
+    const CompactWindow w{s, R - s};
+    int32_t rc = compact_pass(e, nullptr, epoch_now, &w, stats);
     if (rc == RRDB_OK) {
         if (first_run_out)
             *first_run_out = s;
@@ -3536,7 +3576,7 @@ struct SplitTmp {
     uint64_t *ksz = nullptr, *kpos = nullptr, *vsz = nullptr, *vpos = nullptr;
     uint64_t *row_ksrc = nullptr, *row_vsrc = nullptr, *kanch = nullptr, *vanch = nullptr;
     uint64_t *psc_k = nullptr, *psc_v = nullptr;
-    hipEvent_t ev[2] = {};
+    PhaseEvents<2> ev;
     double emit_ms = 0.0;
 };
 
@@ -3557,13 +3597,11 @@ static bool split_emit_side(HipEngine *e, const RunBuf &src, const SplitRunInfo 
                            fv ? nullptr : t.vsz, e->stream);
         if (!fk) {
             launch_psum(t.ksz, t.kpos, n, t.psc_k, e->stream);
-            HIP_OK(hipMemcpyAsync(&tot[0], t.kpos + n - 1, 8, hipMemcpyDeviceToHost, e->stream));
-            HIP_OK(hipMemcpyAsync(&tot[1], t.ksz + n - 1, 8, hipMemcpyDeviceToHost, e->stream));
+            scan_tail_async(t.kpos, t.ksz, n, &tot[0], e->stream);
         }
         if (!fv) {
             launch_psum(t.vsz, t.vpos, n, t.psc_v, e->stream);
-            HIP_OK(hipMemcpyAsync(&tot[2], t.vpos + n - 1, 8, hipMemcpyDeviceToHost, e->stream));
-            HIP_OK(hipMemcpyAsync(&tot[3], t.vsz + n - 1, 8, hipMemcpyDeviceToHost, e->stream));
+            scan_tail_async(t.vpos, t.vsz, n, &tot[2], e->stream);
         }
         HIP_OK(hipStreamSynchronize(e->stream));
         if (!fk)
@@ -3574,17 +3612,17 @@ static bool split_emit_side(HipEngine *e, const RunBuf &src, const SplitRunInfo 
     RunBuf r;
     if (!e->alloc_base(r, ns, kbytes, vbytes, RunAlloc::Try))
         return false;
-    HIP_OK(hipEventRecord(t.ev[0], e->stream));
+    t.ev.record(0, e->stream);
     launch_split_scatter(src.keys, src.koff, src.vals, src.voff, src.sk, n, fk, fv, si.side,
                          (uint32_t)s, si.wbase + (s ? si.nw : 0), s ? si.cnt[0] : 0, t.kpos,
                          t.vpos, ns, kbytes, vbytes, r.koff, r.voff, r.sk, t.row_ksrc,
                          t.row_vsrc, e->stream);
     launch_split_copy(t.row_ksrc, r.koff, ns, fk, kbytes, t.kanch, r.keys, e->stream);
     launch_split_copy(t.row_vsrc, r.voff, ns, fv, vbytes, t.vanch, r.vals, e->stream);
-    HIP_OK(hipEventRecord(t.ev[1], e->stream));
+    t.ev.record(1, e->stream);
     HIP_OK(hipStreamSynchronize(e->stream));
     float ms = 0;
-    if (hipEventElapsedTime(&ms, t.ev[0], t.ev[1]) == hipSuccess)
+    if (t.ev.ms(0, 1, &ms))
         t.emit_ms += ms;
     /* a subset of a fixed-stride run is fixed-stride.  The put-stride is
      * "the length every PUT shares" and is 0 for a run without PUTs
@@ -3647,25 +3685,15 @@ int32_t rrdb_split(void *parent, void *child, int32_t new_partition_count,
         max_kb = std::max(max_kb, run_kb[i]);
         max_vb = std::max(max_vb, run_vb[i]);
     }
-    hipEvent_t ev[4];
-    for (auto &x : ev)
-        HIP_OK(hipEventCreate(&x));
+    PhaseEvents<4> ev;
     SplitTmp t;
-    HIP_OK(hipEventCreate(&t.ev[0]));
-    HIP_OK(hipEventCreate(&t.ev[1]));
-    auto drop_events = [&] {
-        for (auto &x : ev)
-            (void)hipEventDestroy(x);
-        (void)hipEventDestroy(t.ev[0]);
-        (void)hipEventDestroy(t.ev[1]);
-    };
-    HIP_OK(hipEventRecord(ev[0], p->stream));
+    ev.record(0, p->stream);
 
     /* classify + rank every run; one sync for all the counts */
     std::vector<SplitRunInfo> info(R);
     const uint64_t mask = (uint64_t)npc - 1;
     uint64_t *h_cnt = (uint64_t *)p->pinned_buf((R ? R : 1) * 4 * 8);
-    HIP_OK(hipEventRecord(ev[1], p->stream));
+    ev.record(1, p->stream);
     for (size_t i = 0; i < R; i++) {
         const RunBuf &r = p->runs[i];
         SplitRunInfo &si = info[i];
@@ -3691,7 +3719,7 @@ int32_t rrdb_split(void *parent, void *child, int32_t new_partition_count,
         HIP_OK(hipMemcpyAsync(&h_cnt[4 * i + 3], d_has_put, 8, hipMemcpyDeviceToHost,
                               p->stream));
     }
-    HIP_OK(hipEventRecord(ev[2], p->stream));
+    ev.record(2, p->stream);
     HIP_OK(hipStreamSynchronize(p->stream));
     for (size_t i = 0; i < R; i++) {
         SplitRunInfo &si = info[i];
@@ -3727,7 +3755,6 @@ int32_t rrdb_split(void *parent, void *child, int32_t new_partition_count,
         if (!split_emit_side(p, p->runs[i], info[i], 1, t, c->bloom_enabled, &nr, &b)) {
             for (auto &r : child_runs)
                 p->free_run(r);
-            drop_events();
             return RRDB_IO_ERROR; /* both handles as before */
         }
         child_runs.push_back(nr);
@@ -3766,15 +3793,14 @@ int32_t rrdb_split(void *parent, void *child, int32_t new_partition_count,
         st.parent_records += np;
         st.parent_bytes += b;
     }
-    HIP_OK(hipEventRecord(ev[3], p->stream));
+    ev.record(3, p->stream);
     HIP_OK(hipStreamSynchronize(p->stream));
     float ms = 0;
-    if (hipEventElapsedTime(&ms, ev[1], ev[2]) == hipSuccess)
+    if (ev.ms(1, 2, &ms))
         p->phase_ms["split_classify"] = ms;
     p->phase_ms["split_emit"] = t.emit_ms;
-    if (hipEventElapsedTime(&ms, ev[0], ev[3]) == hipSuccess)
+    if (ev.ms(0, 3, &ms))
         p->phase_ms["split_total"] = ms;
-    drop_events();
 
     p->runs = parent_runs;
     c->runs = child_runs;
@@ -3997,33 +4023,10 @@ double ms_since(HostClock::time_point t0)
     return std::chrono::duration<double, std::milli>(HostClock::now() - t0).count();
 }
 
-/* the phase events of one call; destroyed on every way out of it */
-template <int N> struct BatchEvents {
-    hipEvent_t ev[N];
-    BatchEvents()
-    {
-        for (auto &x : ev)
-            HIP_OK(hipEventCreate(&x));
-    }
-    BatchEvents(const BatchEvents &) = delete;
-    BatchEvents &operator=(const BatchEvents &) = delete;
-    ~BatchEvents()
-    {
-        for (auto &x : ev)
-            (void)hipEventDestroy(x);
-    }
-    void record(int i, hipStream_t s) { HIP_OK(hipEventRecord(ev[i], s)); }
-    /* false (and *out untouched) when either event has not completed */
-    bool ms(int i, int j, float *out) const
-    {
-        return hipEventElapsedTime(out, ev[i], ev[j]) == hipSuccess;
-    }
-};
-
 /* <p>_sort, <p>_lookup, <p>_apply, <p>_emit, <p>_total from events 0..5:
  * 0-1 sort, 1-2 lookup, 2-3 apply, 4-5 emit (0 when nothing was emitted);
  * the total leaves out the host's wait for the totals between 3 and 4 */
-void batch_phase_timers(HipEngine *e, const char *prefix, const BatchEvents<6> &ev, bool emitted)
+void batch_phase_timers(HipEngine *e, const char *prefix, const PhaseEvents<6> &ev, bool emitted)
 {
     const std::string p(prefix);
     float ms = 0;
@@ -4202,7 +4205,7 @@ int32_t rrdb_write_batch(void *h, uint64_t n_ops, const uint8_t *keys, const uin
         return RRDB_IO_ERROR;
     e->phase_ms["wb_upload"] = ms_since(t_up);
 
-    BatchEvents<4> ev;
+    PhaseEvents<4> ev;
     const WbKeys wk{d_keys, d_koff, in_fk, d_lcp};
     ev.record(0, e->stream);
     const SortedOps so = batch_sort(wk, n, d_lcp, d_w0, d_i0, d_w1, d_i1, e->stream);
@@ -4213,17 +4216,14 @@ int32_t rrdb_write_batch(void *h, uint64_t n_ops, const uint8_t *keys, const uin
                     e->stream);
     launch_psum(d_keep, d_rank, n, d_psc, e->stream);
     uint64_t tot[6] = {0, 0, 0, 0, 0, 0}, red[WBR_WORDS];
-    HIP_OK(hipMemcpyAsync(&tot[0], d_rank + n - 1, 8, hipMemcpyDeviceToHost, e->stream));
-    HIP_OK(hipMemcpyAsync(&tot[1], d_keep + n - 1, 8, hipMemcpyDeviceToHost, e->stream));
+    scan_tail_async(d_rank, d_keep, n, &tot[0], e->stream);
     if (!in_fk) {
         launch_psum(d_ksz, d_kpos, n, d_psc, e->stream);
-        HIP_OK(hipMemcpyAsync(&tot[2], d_kpos + n - 1, 8, hipMemcpyDeviceToHost, e->stream));
-        HIP_OK(hipMemcpyAsync(&tot[3], d_ksz + n - 1, 8, hipMemcpyDeviceToHost, e->stream));
+        scan_tail_async(d_kpos, d_ksz, n, &tot[2], e->stream);
     }
     if (!in_fv) {
         launch_psum(d_vsz, d_vpos, n, d_psc, e->stream);
-        HIP_OK(hipMemcpyAsync(&tot[4], d_vpos + n - 1, 8, hipMemcpyDeviceToHost, e->stream));
-        HIP_OK(hipMemcpyAsync(&tot[5], d_vsz + n - 1, 8, hipMemcpyDeviceToHost, e->stream));
+        scan_tail_async(d_vpos, d_vsz, n, &tot[4], e->stream);
     }
     HIP_OK(hipMemcpyAsync(red, d_red, sizeof(red), hipMemcpyDeviceToHost, e->stream));
     HIP_OK(hipStreamSynchronize(e->stream));
@@ -4356,7 +4356,7 @@ int32_t rrdb_incr_batch(void *h, uint64_t n_ops, const uint8_t *keys, const uint
     if (!b.ok)
         return RRDB_IO_ERROR;
 
-    BatchEvents<6> ev;
+    PhaseEvents<6> ev;
     /* sort, then the segments: one per distinct key */
     const WbKeys wk{d_keys, in_fk ? nullptr : d_koff, in_fk, d_lcp};
     ev.record(0, e->stream);
@@ -4555,7 +4555,7 @@ int32_t rrdb_write_batch_timetag(void *h, uint64_t n_ops, const uint8_t *keys,
         return RRDB_IO_ERROR;
     e->phase_ms["wbt_upload"] = ms_since(t_up);
 
-    BatchEvents<6> ev;
+    PhaseEvents<6> ev;
     /* sort, then the segments: one per distinct key */
     const WbKeys wk{d_keys, in_fk ? nullptr : d_koff, in_fk, d_lcp};
     ev.record(0, e->stream);
@@ -4791,7 +4791,7 @@ int32_t rrdb_check_and_mutate_batch(
     if (!b.ok)
         return RRDB_IO_ERROR;
 
-    BatchEvents<6> ev;
+    PhaseEvents<6> ev;
     /* sort the entries; key heads, hashkey groups, the ops by group */
     const WbKeys wk{d_ekeys, in_fk ? nullptr : d_ekoff, in_fk, d_lcp};
     ev.record(0, e->stream);

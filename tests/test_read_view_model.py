@@ -403,14 +403,17 @@ def test_constants_have_not_drifted():
         assert define(common, name) == getattr(RV, name), name
     for name in ("LDST_CAP", "BLOCK", "WAVE"):
         assert define(kernels, name) == getattr(RV, name), name
-    # the names are what build_view and the view launch use
-    assert "total > VIEW_BT_MIN_RECORDS" in engine
+    # the names are what build_view and the view launch use: build_view hands
+    # the threshold to prepare_rank, which compares the window with it
+    view = engine[engine.index("DevView build_view("):]
+    assert re.search(r"prepare_rank\(dr, 0, R, [^;]*\bVIEW_BT_MIN_RECORDS, true\);", view)
+    assert "if (total > bt_min_records)" in engine
     launch = kernels[kernels.index("void launch_rank_grp_view("):]
     launch = launch[:launch.index("k_rank_grp<1>")]
     assert "blocks > GRP_VIEW_BLOCKS" in launch and "blocks = GRP_VIEW_BLOCKS" in launch
     assert re.search(r"int bt_shift = %d;" % RV.BT_SHIFT_DEFAULT, engine)
     assert "int cshift = bt_shift + 6;" in engine and "(wmax >> cshift) > 8" in engine
-    # gs_of restates build_anchors
+    # gs_of restates grp_shift, which build_anchors and the count scan call
     assert "while ((1ull << (gs + 1)) * (uint64_t)R <= GRP_TARGET && gs < 8)" in engine
     assert [RV.gs_of(R) for R in (2, 3, 8, 32)] == [8, 8, 7, 5]
     # the route numbering and the report's layout, as capi.py mirrors them

@@ -11,7 +11,8 @@ Three layers, all exact (integers and bytes, no tolerance):
       every (engine.rank_mode, engine.emit_mode), asserting the route that
       rrdb_last_compact_route reports, the full stats and a full drain with
       expire headers against the oracle and tests/pymodel.py; the rewriting
-      sets again under data versions 0 and 2; one window pass;
+      sets again under data versions 0 and 2; one window pass; writes and a
+      scan between the begin and the finish of a split pass, per emit kernel;
   2c  (no GPU) the oracle against pymodel on the same rule sets, and a
       self-check that no rule set passes vacuously.
 """
@@ -27,7 +28,8 @@ from incubator_pegasus_amd import data as D
 from incubator_pegasus_amd.capi import (NOT_FOUND, OK, ROUTE_EMIT_CHUNKED,
                                         ROUTE_EMIT_CHUNKED_FIXED, ROUTE_EMIT_INPUT,
                                         ROUTE_EMIT_RANK, ROUTE_NONE, ROUTE_RANK_GLOBAL,
-                                        ROUTE_RANK_GRP, ROUTE_RANK_LDS, ROUTE_RANK_LDST)
+                                        ROUTE_RANK_GRP, ROUTE_RANK_LDS, ROUTE_RANK_LDST,
+                                        SCAN_COMPLETED)
 from pymodel import Model, expire_of
 from rule_tables import (EPOCH_BEGIN, LAYOUTS, NOW, PATTERN_CASES, REWRITING, SMT_ANYWHERE,
                          SMT_NAMES, SMT_PREFIX, TTL_HI, TTL_LO, TTL_RANGE_CASES, RuleSet,
@@ -331,7 +333,7 @@ G, L, T, P = ROUTE_RANK_GLOBAL, ROUTE_RANK_LDS, ROUTE_RANK_LDST, ROUTE_RANK_GRP
 RK, IN, CH, FX = (ROUTE_EMIT_RANK, ROUTE_EMIT_INPUT, ROUTE_EMIT_CHUNKED,
                   ROUTE_EMIT_CHUNKED_FIXED)
 # (engine.rank_mode, engine.emit_mode, layout) -> (rank, emit), from a reading
-# of compact_begin / compact_finish for a manual pass over 3 runs that emits
+# of plan_pass / rank_pass / emit_pass for a manual pass over 3 runs that emits
 # at least one record:
 #   rank  lds   iff rank_mode == lds and emit_mode == chunked (R > 1);
 #         grp   else iff rank_mode == grp, emit_mode != input, R <= 32 and the
@@ -432,6 +434,102 @@ def test_finish_emits_what_begin_prepared(oracle_lib, hip_lib, begun, later, emi
         assert g.last_compact_route() == (G, emit)
         assert stats_dict(sg) == mstats
         assert drain(g, 0) == rows
+    finally:
+        g.close()
+
+
+# ---- writes between begin and finish ----
+# rrdb_put and rrdb_remove are accepted while a pass is pending, and the next
+# read flushes them: a run is appended and the device run table is rebuilt.
+# The pass merges exactly the runs that existed at begin, from its own copy of
+# their rows, and the flushed run stays behind the merged one.
+
+NO_RULES = RuleSet("no_rules", None, 0, True, False)  # does nothing to the written keys
+
+
+def _new_key(layout):
+    """(hashkey, sortkey, user data) of a key no run holds, in the layout's
+    key and value format, so the flushed run keeps the layout's strides"""
+    if layout == "var":
+        return b"hashkey-new", b"sortkey-new", b"written"
+    hk, sk = b"hkwxyzNEWK", b"n001"  # the shared first 8 bytes, 10 + 4 like the others
+    assert hk not in LAYOUTS[layout].hashkeys and len(hk) == len(LAYOUTS[layout].hashkeys[0])
+    return hk, sk, b"r%011d" % 424242
+
+
+def _write_in_window(g, layout, rows):
+    """put a new key, put over one surviving key, remove another: the writes,
+    and `rows` with them overlaid (expire 0: no TTL)"""
+    hk, sk, data = _new_key(layout)
+    new = D.generate_key(hk, sk)
+    held = [k for k, _, _ in rows]
+    assert new not in held and len(held) > 6
+    over, gone = held[len(held) // 3], held[2 * len(held) // 3]
+    assert g.put(hk, sk, data) == OK
+    assert g.put(*D.restore_key(over), data[::-1]) == OK
+    assert g.remove(*D.restore_key(gone)) == OK
+    want = [r for r in rows if r[0] not in (over, gone)] + [(new, data, 0), (over, data[::-1], 0)]
+    return (hk, sk, data), sorted(want)
+
+
+WINDOW_WRITE_ROUTES = [r for r in ROUTE_TABLE if r[:3] in (("grp", "chunked", "word"),
+                                                           ("global", "chunked", "var"),
+                                                           ("grp", "rank", "word"),
+                                                           ("ldst", "input", "word"))]
+
+
+@gpu
+@pytest.mark.parametrize("rank_mode,emit_mode,layout,want", WINDOW_WRITE_ROUTES,
+                         ids=[_route_id(r) for r in WINDOW_WRITE_ROUTES])
+def test_writes_between_begin_and_finish(oracle_lib, hip_lib, rank_mode, emit_mode, layout, want):
+    assert {r[3][1] for r in WINDOW_WRITE_ROUTES} == {CH, FX, RK, IN}
+    mstats, rows = reference(oracle_lib, layout, NO_RULES)
+    g = open_part(hip_lib)
+    try:
+        g.set_envs({"engine.rank_mode": rank_mode, "engine.emit_mode": emit_mode})
+        for run in build_runs(layout):
+            g.ingest_run(run)
+        assert g.manual_compact_begin(NOW) == OK
+        (hk, sk, data), overlaid = _write_in_window(g, layout, rows)
+        # the first read flushes: a fourth run, a new device run table
+        assert g.get(D.generate_key(hk, sk), 0) == (OK, data)
+        assert g.num_runs() == 4
+        assert g.multi_get(hk, 0) == (OK, [(sk, data)])
+        err, sg = g.manual_compact_finish()
+        assert err == OK
+        assert g.last_compact_route() == want
+        assert stats_dict(sg) == mstats  # the three runs of begin, nothing of the fourth
+        assert g.num_runs() == 2
+        assert drain(g, 0) == overlaid
+        assert g.manual_compact(NOW)[0] == OK
+        assert g.num_runs() == 1
+        assert drain(g, 0) == overlaid
+    finally:
+        g.close()
+
+
+@gpu
+def test_view_between_begin_and_finish(oracle_lib, hip_lib):
+    """The same window with a scan in it: scan_open builds a view over the
+    four runs, through the rank preparation the pass used, while the pass's
+    arrays are pinned.  The finish frees the window's runs, so the parked
+    context is gone, as after any compaction."""
+    mstats, rows = reference(oracle_lib, "word", NO_RULES)
+    g = open_part(hip_lib)
+    try:
+        for run in build_runs("word"):
+            g.ingest_run(run)
+        assert g.manual_compact_begin(NOW) == OK
+        hk, sk, data = _new_key("word")
+        assert g.put(hk, sk, data) == OK
+        res = g.scan_open(b"\x00\x00", b"\xff\xff", 0, batch_size=5, validate_partition_hash=False)
+        assert res.error == OK and len(res.kvs) == 5 and res.context_id != SCAN_COMPLETED
+        assert g.last_view_route().rank == ROUTE_RANK_GRP
+        err, sg = g.manual_compact_finish()
+        assert err == OK and stats_dict(sg) == mstats
+        assert g.scan_next(res.context_id, 0).error == NOT_FOUND
+        assert g.num_runs() == 2
+        assert drain(g, 0) == sorted(rows + [(D.generate_key(hk, sk), data, 0)])
     finally:
         g.close()
 
